@@ -1,6 +1,6 @@
 """Benchmark of the aggforce force-map hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One step = one full ``project_forces`` (Gram build -> [all-reduce] -> constrained solve ->
 map coordinates and forces -> residual) over a synthetic trajectory that is already resident
@@ -90,7 +90,16 @@ def parse(argv=None):
     p.add_argument("--rehearse-on-one-gpu", action="store_true",
                    help="N > 1 ranks that all use cuda:0 and talk over gloo (RCCL refuses two ranks on one device): "
                         "exercises the multi-rank code path on a one-GPU box; NOT a measurement")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy "
+                        "(float32 / float64, at most 64 MB in all; the mapped trajectories as a fixed, seeded frame "
+                        "sample when they are larger): the force map, the residual, mapped_forces, mapped_coords")
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.dry_run:
+        p.error("--dump-outputs needs a run that computes (not --dry-run)")
+    return a
 
 
 def free_port():
@@ -168,6 +177,56 @@ def replicated_spread(t, world):
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)
     dist.all_reduce(lo, op=dist.ReduceOp.MIN)
     return float((hi - lo).abs().max().item())
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: all arrays together; below 64 MB (decimal) with the .npy headers
+
+
+def sample_frames(a, idx, begin, world):
+    """Rows ``idx`` (sorted global frame numbers) of the frame-sharded array ``a`` (this rank holds frames
+    begin..begin + len(a)), as a host array in a's dtype on every rank.  With N > 1 ranks each rank fills the rows
+    it holds into a zero float64 buffer and one sum all-reduce assembles them: every row is non-zero on one rank
+    only, and float32 survives the round trip through float64 exactly."""
+    import torch
+
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    mine = (idx >= begin) & (idx < begin + t.shape[0])
+    rows = t[torch.from_numpy(idx[mine] - begin).to(t.device)]
+    if world == 1:
+        return rows.cpu().numpy()
+    import torch.distributed as dist
+
+    buf = torch.zeros((len(idx),) + tuple(t.shape[1:]), dtype=torch.float64, device="cuda")
+    buf[torch.from_numpy(np.flatnonzero(mine)).cuda()] = rows.to("cuda", torch.float64)
+    dist.all_reduce(buf)
+    return buf.to(rows.dtype).cpu().numpy()
+
+
+def dump_outputs(out_dir, out, solved, solved_name, T_total, begin, world, rank):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy.  The fitted map and the
+    residual are replicated on every rank; mapped_forces / mapped_coords are frame-sharded and share what is left of
+    DUMP_BYTES: all frames when they fit, else the same seeded sample of frames for both (fixed by SEED and the total
+    frame count, so runs with equal arguments dump equal frames whatever the GPU count).  Returns {name: shape}."""
+    arrays = {solved_name: np.asarray(solved, dtype=np.float64), "residual": np.asarray(out["residual"], np.float64)}
+    mapped = {k: out[k] for k in ("mapped_forces", "mapped_coords")}
+    room = (DUMP_BYTES - sum(v.nbytes for v in arrays.values())) // len(mapped)
+    row_bytes = max(int(np.prod(v.shape[1:])) * (v.element_size() if hasattr(v, "element_size") else v.dtype.itemsize)
+                    for v in mapped.values())
+    n = min(T_total, room // row_bytes)
+    idx = (np.arange(T_total, dtype=np.int64) if n == T_total
+           else np.sort(np.random.default_rng(SEED).choice(T_total, size=n, replace=False)).astype(np.int64))
+    for k, v in mapped.items():
+        arrays[k] = sample_frames(v, idx, begin, world)
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            arrays[k] = v.astype(np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES} byte budget"
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for k, v in arrays.items():
+            np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def profiled_traffic(workload, world):
@@ -501,11 +560,16 @@ def main():
         cons_resid = (float(np.max(np.abs(cmap.standard_matrix @ W.T - np.eye(n_cg))))
                       if W.shape[1] == cmap.standard_matrix.shape[1] else None)
         solved = np.asarray(W, dtype=np.float64)
+        solved_name = "force_map"
     else:
         cons_resid = None
         solved = np.stack([np.asarray(c, dtype=np.float64) for c in fmap.tags["coef_list"]])
+        solved_name = "force_map_coefs"
     # the solve is replicated, not broadcast: every rank must hold the same map, bit for bit
     w_spread = replicated_spread(torch.from_numpy(np.ascontiguousarray(solved)).cuda(), world)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, out, solved, solved_name, T_total, begin, world, rank)
     world_seen = 1
     if comm is not None:
         import torch.distributed as dist
@@ -616,6 +680,8 @@ def main():
             },
             "roofline": roof,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and not args.no_cpu_baseline:
             del out
             npdt = np.float64 if dt == "f64" else np.float32

@@ -124,3 +124,47 @@ def test_bench_kernel_label_is_the_string_rocprofv3_prints(tmp_path):
         assert stats, "rocprofv3 wrote no kernel_stats.csv"
         seen = [row.split('","')[0].strip('"') for f in stats for row in open(f).read().splitlines()[1:]]
         assert any(s.startswith("void " + name + "(") for s in seen), (name, [s for s in seen if family in s])
+
+
+def test_bench_dump_outputs_are_what_the_timed_step_returned(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: the last timed step's results as float .npy files within 64 MB -- the same bits from two
+    runs with equal arguments, the same frames at any rank count, and equal to the force map applied to the inputs.
+    200000 frames of `tiny` are more than the budget holds, so the mapped trajectories are a seeded frame sample."""
+    import numpy as np
+    import torch
+
+    monkeypatch.delenv("HSA_ENABLE_IPC_MODE_LEGACY", raising=False)  # restored after the test: bench sets a default
+    import bench
+    from aggforce_amd import _kernels as K
+
+    T = 200000
+    flags = ("--workload", "tiny", "--frames", str(T), "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    lines = {name: run_bench(*flags, "--dump-outputs", str(tmp_path / name)) for name in ("a", "b")}
+    lines["r"] = run_bench(*flags, "--gpus", "2", "--rehearse-on-one-gpu", "--dump-outputs", str(tmp_path / "r"))
+    names = {"force_map", "residual", "mapped_forces", "mapped_coords"}
+    dumps = {}
+    for name, line in lines.items():
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == sorted(n + ".npy" for n in names), files
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 * 10**6
+        dumps[name] = {n: np.load(tmp_path / name / (n + ".npy")) for n in names}
+        assert all(v.dtype in (np.float32, np.float64) for v in dumps[name].values())
+        assert line["dumped_outputs"]["arrays"] == {n: list(v.shape) for n, v in dumps[name].items()}
+        assert float(dumps[name]["residual"]) == line["config"]["residual"]
+    a, b, r = dumps["a"], dumps["b"], dumps["r"]
+    for n in names:
+        assert np.array_equal(a[n], b[n]), n  # bit-reproducible, inputs included
+    n_rows = a["mapped_forces"].shape[0]
+    assert 0 < n_rows < T and a["mapped_coords"].shape == a["mapped_forces"].shape == (n_rows, 16, 3)
+    # two shards assemble the same sampled frames; only the Gram's summation order differs
+    assert np.array_equal(r["mapped_coords"], a["mapped_coords"])
+    assert np.abs(r["force_map"] - a["force_map"]).max() < 1e-9
+    assert np.abs(r["mapped_forces"] - a["mapped_forces"]).max() < 1e-9 * np.abs(a["mapped_forces"]).max()
+    # the dumped frames are the documented seeded sample, mapped by the dumped force map
+    idx = np.sort(np.random.default_rng(bench.SEED).choice(T, size=n_rows, replace=False))
+    forces = K.synth_normal(T, 256, torch.float64, bench.SEED, sigma=30.0)[torch.from_numpy(idx).cuda()].cpu().numpy()
+    coords = K.synth_normal(T, 256, torch.float64, bench.SEED + 1, sigma=0.3, lattice=1.5)[torch.from_numpy(idx).cuda()]
+    expect = np.einsum("cf,tfd->tcd", a["force_map"], forces)
+    assert np.abs(a["mapped_forces"] - expect).max() < 1e-10 * np.abs(expect).max()
+    assert np.array_equal(a["mapped_coords"], coords[:, 0:256:16].cpu().numpy())
