@@ -1,6 +1,6 @@
 """Benchmark of the aggforce force-map hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = one full ``project_forces`` (Gram build -> [all-reduce] -> constrained solve ->
 map coordinates and forces -> residual) over a synthetic trajectory that is already resident
@@ -14,9 +14,10 @@ before anything touches the GPU it starts ``python -m torch.distributed.run --np
 on this same file as a child, forwards rank 0's JSON line and exits with the child's code.
 
 Rank 0 prints ONE JSON line: metric / value (frames/s, whole job) / roofline of the dominant
-kernel (MFMA SYRK, HIP-event timed inside this run) / cpu_baseline (the NumPy oracle = a port
-of the reference's qplinear.py operation sequence, timed on this box's host cores on a bounded
-frame sample, N=1 only).
+kernel (MFMA SYRK, HIP-event timed inside this run).  A plain run stops there: set-up, warm-up,
+the timed steps, --dump-outputs, the line.  With --full (N=1 only) the line also carries
+cpu_baseline (the NumPy oracle = a port of the reference's qplinear.py operation sequence, timed
+on this box's host cores on a bounded frame sample; at c3 tens of seconds of host work).
 """
 import argparse
 import json
@@ -80,10 +81,14 @@ def parse(argv=None):
                         "zeronet = every frame's forces sum to zero (isolated molecule: P singular along the all-ones "
                         "vector, qplinear.py:71-86); dense = centre-of-mass coordinate map over contiguous blocks "
                         "(map/core.py:219-240: a second full K3 pass instead of the slice gather)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU baseline after the timed steps "
+                        "(N = 1 only). Off by default, so a plain run does set-up, warm-up, the timed steps and "
+                        "--dump-outputs only")
     p.add_argument("--cpu-frames", type=int, default=20000,
-                   help="frame sample of the CPU baseline (c3: ~20 s of host work: 2 GB of forces, two 2e12-flop matmuls, "
-                        "the single-threaded einsum apply)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="with --full: frame sample of the CPU baseline (c3: ~20 s of host work: 2 GB of forces, two "
+                        "2e12-flop matmuls, the single-threaded einsum apply)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher self-test on CPU (gloo, no GPU, no product compute): NOT a measurement")
     p.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
@@ -682,7 +687,7 @@ def main():
         }
         if dumped is not None:
             line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del out
             npdt = np.float64 if dt == "f64" else np.float32
             cm_host = np.asarray(cmap.standard_matrix, dtype=np.float64)

@@ -54,8 +54,9 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
 @pytest.mark.parametrize("variant", ["pairs", "zeronet", "dense"])
 def test_bench_variants_of_the_linear_workload(variant):
     """SURVEY 8(d)'s synthetic-input variants, small: the line is well formed, the map is feasible, and the
-    CPU port beside it ran the same variant."""
-    line = run_bench("--workload", "tiny", "--variant", variant, "--steps", "1", "--warmup", "1", "--cpu-frames", "512")
+    CPU port beside it (--full) ran the same variant."""
+    line = run_bench("--workload", "tiny", "--variant", variant, "--steps", "1", "--warmup", "1", "--full",
+                     "--cpu-frames", "512")
     cfg = line["config"]
     assert cfg["variant"] == variant and ("+" + variant) in cfg["workload"]
     assert cfg["constraint_residual"] < 1e-8 and line["value"] > 0

@@ -60,19 +60,32 @@ def test_random_k6_and_k5_sweeps_match_oracle(monkeypatch, capsys):
 
 
 def test_bench_contract_on_tiny_workload():
-    """bench.py prints exactly one JSON line on stdout with the fields the driver reads."""
+    """bench.py prints exactly one JSON line on stdout with the fields the driver reads; --full adds the CPU baseline,
+    which a plain run leaves out."""
     import json
     import subprocess
 
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2",
-                          "--warmup", "1", "--cpu-frames", "64"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
-    assert len(lines) == 1
-    d = json.loads(lines[0])
-    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+    def run(*flags):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2",
+                              "--warmup", "1", *flags], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "config", "roofline")
+    plain = run()
+    for key in keys:
+        assert key in plain, key
+    assert "cpu_baseline" not in plain
+    d = run("--full", "--cpu-frames", "64")
+    for key in keys + ("cpu_baseline",):
         assert key in d, key
+    # --full adds to the line; what the steps computed and how the headline is labelled do not change
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert d[key] == plain[key], key
+    assert d["config"]["residual"] == plain["config"]["residual"]
     assert d["unit"] == "frames/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["higher_is_better"] is True and d["scaling"] in ("weak", "strong") and d["vs_baseline"] is None
     assert d["value"] > 0 and d["ms_per_step"] > 0 and "workload" in d["config"]

@@ -3,10 +3,13 @@
 #   bash tools/profile_round4.sh a   -> c3 and its variants          (profiles/r04_c3*)
 #   bash tools/profile_round4.sh b   -> c1, c2, c4, c5               (profiles/r04_c{1,2,4,5}*)
 #   bash tools/profile_round4.sh c   -> bench lines with the CPU baseline, stream kernels, next rows, small-system ablations
+# Logs and bench lines go to the folder PROFILE_OUT names (the one tools/profile_gpu.sh writes to);
+# bench lines are --full runs.
 # Afterwards, in the build container:  for t in ...; do python tools/commit_profile.py r04_$t "<bench args>"; done
 set -o pipefail
 part=${1:-a}
-run() { tag=$1; shift; bash tools/profile_gpu.sh $tag "$@" > gpurun_out/$tag.log 2>&1; tail -1 gpurun_out/$tag.log; }
+out=${PROFILE_OUT:?set PROFILE_OUT to the output folder}
+run() { tag=$1; shift; bash tools/profile_gpu.sh $tag "$@" > "$out"/$tag.log 2>&1; tail -1 "$out"/$tag.log; }
 if [ "$part" = a ]; then
   PASSES="fetch write dram mfma" run r04_c3 --workload c3 --steps 3 --warmup 1
   PASSES="fetch mfma" run r04_c3pairs --workload c3 --variant pairs --steps 3 --warmup 1
@@ -19,13 +22,13 @@ elif [ "$part" = b ]; then
   PASSES="fetch mfma" run r04_c4 --workload c4 --steps 3 --warmup 1
 else
   for w in c3 c2 c1 c4 c5; do
-    timeout -k 10 600 python bench.py --workload $w > gpurun_out/r04_bench_$w.json 2> gpurun_out/r04_bench_$w.err || echo "bench $w failed"
-    tail -c 160 gpurun_out/r04_bench_$w.json; echo
+    timeout -k 10 600 python bench.py --full --workload $w > "$out"/r04_bench_$w.json 2> "$out"/r04_bench_$w.err || echo "bench $w failed"
+    tail -c 160 "$out"/r04_bench_$w.json; echo
   done
   for v in pairs zeronet dense; do
-    timeout -k 10 600 python bench.py --workload c3 --variant $v > gpurun_out/r04_bench_c3_$v.json 2> gpurun_out/r04_bench_c3_$v.err || echo "bench $v failed"
+    timeout -k 10 600 python bench.py --full --workload c3 --variant $v > "$out"/r04_bench_c3_$v.json 2> "$out"/r04_bench_c3_$v.err || echo "bench $v failed"
   done
-  timeout -k 10 300 python tools/next_rows_bench.py > gpurun_out/r04_next_rows.jsonl 2> gpurun_out/r04_next_rows.err; tail -2 gpurun_out/r04_next_rows.jsonl
-  timeout -k 10 300 python tools/stream_kernels_bench.py > gpurun_out/r04_stream_kernels.jsonl 2> gpurun_out/r04_stream_kernels.err; tail -2 gpurun_out/r04_stream_kernels.jsonl
-  bash tools/small_ablate.sh > gpurun_out/r04_small_ablate_run.jsonl 2>&1; tail -2 gpurun_out/r04_small_ablate_run.jsonl
+  timeout -k 10 300 python tools/next_rows_bench.py > "$out"/r04_next_rows.jsonl 2> "$out"/r04_next_rows.err; tail -2 "$out"/r04_next_rows.jsonl
+  timeout -k 10 300 python tools/stream_kernels_bench.py > "$out"/r04_stream_kernels.jsonl 2> "$out"/r04_stream_kernels.err; tail -2 "$out"/r04_stream_kernels.jsonl
+  bash tools/small_ablate.sh > "$out"/r04_small_ablate_run.jsonl 2>&1; tail -2 "$out"/r04_small_ablate_run.jsonl
 fi
