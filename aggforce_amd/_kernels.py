@@ -1025,3 +1025,66 @@ def pair_pool_term(var_r: torch.Tensor, mean_r: torch.Tensor, mean: torch.Tensor
     check(lib().aggf_pair_pool_term(ptr(var_r), ptr(mean_r), ptr(mean), float(weight), var_r.numel(), ptr(var_r),
                                     stream_ptr()), "aggf_pair_pool_term")
     return var_r
+
+
+# ------------------------------------------------------------------ K7 map validation
+
+
+def gauss_pair_forces(x: torch.Tensor, offset: float, width: float, want_forces: bool = True,
+                      want_energies: bool = False):
+    """(G (T, n, 3) or None, E (T,) or None) in x's dtype for one squared-distance Gaussian; see aggf_gauss_pair_forces."""
+    l = lib()
+    T, n, _ = x.shape
+    G = torch.empty_like(x) if want_forces else None
+    E = torch.empty(T, dtype=x.dtype, device=x.device) if want_energies else None
+    if x.numel() == 0:
+        return G, E
+    need = l.aggf_gauss_pair_forces_workspace_bytes(T, n) if want_energies else 0
+    ws = workspace(need, x.device, "mapval") if want_energies else None
+    with _timed("gauss_forces"):
+        check(l.aggf_gauss_pair_forces(ptr(x), T, n, dtype_code(x.dtype), float(offset), float(width), ptr(G), ptr(E),
+                                       ptr(ws), need, stream_ptr()), "aggf_gauss_pair_forces")
+    return G, E
+
+
+def gauss_proj(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float) -> torch.Tensor:
+    """(S,) float64: sum over frames and sites of F . G_s for every offset; see aggf_gauss_proj."""
+    l = lib()
+    T, n, _ = x.shape
+    S = offsets.numel()
+    out = torch.empty(S, dtype=torch.float64, device=x.device)
+    need = l.aggf_gauss_proj_workspace_bytes(T, n, S)
+    ws = workspace(need, x.device, "mapval")
+    with _timed("gauss_proj"):
+        check(l.aggf_gauss_proj(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
+                                float(width), ptr(out), ptr(ws), need, stream_ptr()), "aggf_gauss_proj")
+    return out
+
+
+def gauss_shift(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float):
+    """((S,), (S,)) float64: sum F . G_s and sum |G_s|^2 for every offset, one pass; see aggf_gauss_shift."""
+    l = lib()
+    T, n, _ = x.shape
+    S = offsets.numel()
+    ip = torch.empty(S, dtype=torch.float64, device=x.device)
+    gsq = torch.empty(S, dtype=torch.float64, device=x.device)
+    need = l.aggf_gauss_shift_workspace_bytes(T, n, S)
+    ws = workspace(need, x.device, "mapval")
+    with _timed("gauss_shift"):
+        check(l.aggf_gauss_shift(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
+                                 float(width), ptr(ip), ptr(gsq), ptr(ws), need, stream_ptr()), "aggf_gauss_shift")
+    return ip, gsq
+
+
+def dot(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Device scalar (shape (1,), float64): sum a * b over equally sized arrays, fixed summation order."""
+    l = lib()
+    assert a.numel() == b.numel() and a.is_contiguous() and b.is_contiguous()
+    out = torch.zeros(1, dtype=torch.float64, device=a.device)
+    if a.numel() == 0:
+        return out
+    need = l.aggf_dot_workspace_bytes()
+    ws = workspace(need, a.device, "dot")
+    check(l.aggf_dot(ptr(a), dtype_code(a.dtype), ptr(b), dtype_code(b.dtype), a.numel(), ptr(out), ptr(ws), need,
+                     stream_ptr()), "aggf_dot")
+    return out

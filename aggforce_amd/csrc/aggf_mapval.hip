@@ -1,0 +1,566 @@
+// K7: map validation with random Gaussian pair-potential force fields (reference jaxmapval.py).
+//
+// One Gaussian of the SQUARED pair distance, g(x) = exp(-((x - o) / w)^2), x = |r_i - r_j|^2, summed over the full
+// n x n matrix of a frame (sq_gaussian_energies, jaxmapval.py:365-392), has the forces (the diagonal drops out)
+//     G_i = (8 / w^2) sum_j (x_ij - o) g(x_ij) (r_i - r_j).
+// The reference materialises G (T, n, 3) once per random offset o_s and reduces it against the mapped forces.  Here:
+//   * gauss_site_forces_kernel: G and the frame energies for ONE offset (sq_gaussian_forces / _energies);
+//   * gauss_proj_kernel:  P_s = sum_t sum_i F_i . G_s,i for S offsets in one pass, in the pair form
+//         sum_{i<j} (x - o_s) g_s(x) u,   u = (r_i - r_j) . (F_i - F_j)   (times 8 / w^2):
+//     a workgroup takes a range of (frame, pair) entries, forms (x, u) once per entry into LDS, and every thread runs
+//     its MV_SC offsets (registers) over the staged list -- all lanes read the same LDS word (broadcast);
+//   * gauss_shift_kernel: sum F . G_s and sum |G_s|^2 for S offsets in one pass, in the per-site form (|G_s|^2 needs
+//     the per-site sums): a workgroup walks its frames and sites i, accumulates G_s,i over j from the frame's
+//     coordinates in LDS (tiled over j above MV_JT sites), and folds F_i . G_s,i and |G_s,i|^2 into per-sample sums.
+//     Each thread owns a chunk of samples, so those sums need no cross-lane reduction;
+//   * dot_kernel: sum a * b in a fixed order (mscg_ip and the generic loop of random_force_proj / _residual_shift).
+// Precision: float64 when either input is float64, float32 with the hardware exp2 when both are float32; every sum
+// over pairs, sites and frames is float64.  Partial sums go to slabs (one per workgroup) and are combined in a fixed
+// order: two runs are bit-identical.  x is formed from the differences r_i - r_j.
+#include "aggf_common.h"
+
+namespace aggf {
+
+constexpr int MV_THREADS = 256;
+constexpr int MV_SC = 4;                         // offsets per thread (registers)
+constexpr int MV_SCHUNK = MV_THREADS * MV_SC;    // offsets per workgroup (grid y)
+constexpr int MV_JT = 1024;                      // sites per LDS stage of the per-site kernels (24 KiB in float64)
+constexpr int MV_PL = 1024;                      // (x, u) entries per LDS stage of the projection kernel
+constexpr int64_t MV_TARGET_WGS = 2048;          // workgroups a split plan aims for (8 per CU)
+constexpr int64_t MV_SLAB_MAX = (int64_t)1 << 26;  // slab doubles at most (512 MiB)
+constexpr int MV_DOT_BLOCKS = 1024;
+constexpr int64_t MV_MAX_GRID = 65536;
+
+template <typename A, typename B>
+struct Promote {
+  typedef double type;
+};
+template <>
+struct Promote<float, float> {
+  typedef float type;
+};
+
+// g = exp(-(tt^2) / w^2) with k = coef(w): float32 uses v_exp_f32 (exp2, log2(e) folded into k), float64 the libm exp
+template <typename C>
+struct Gauss;
+template <>
+struct Gauss<float> {
+  __host__ __device__ static float coef(double width) { return (float)(1.4426950408889634074 / (width * width)); }
+  __device__ static __forceinline__ float g(float tt, float k) { return __builtin_amdgcn_exp2f(-(tt * tt) * k); }
+};
+template <>
+struct Gauss<double> {
+  __host__ __device__ static double coef(double width) { return 1.0 / (width * width); }
+  __device__ static __forceinline__ double g(double tt, double k) { return exp(-(tt * tt) * k); }
+};
+
+// x = |d|^2 summed left to right with no fused multiply-add: x - o cancels near the offset, and this is the
+// rounding of the float64 restatement the tests compare with
+template <typename C>
+__device__ __forceinline__ C sq_norm3(C d0, C d1, C d2) {
+#pragma clang fp contract(off)
+  return d0 * d0 + d1 * d1 + d2 * d2;
+}
+
+// pair index p in [0, n (n - 1) / 2) -> (i, j), i < j, row by row of the strict upper triangle
+__device__ __forceinline__ int64_t pair_row_start(int64_t i, int64_t n) { return i * (n - 1) - i * (i - 1) / 2; }
+__device__ __forceinline__ void pair_of(int64_t p, int64_t n, int64_t* pi, int64_t* pj) {
+  const double b = (double)(2 * n - 1);
+  int64_t i = (int64_t)((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
+  if (i < 0) i = 0;
+  if (i > n - 2) i = n - 2;
+  while (i > 0 && pair_row_start(i, n) > p) --i;
+  while (i < n - 2 && pair_row_start(i + 1, n) <= p) ++i;
+  *pi = i;
+  *pj = i + 1 + (p - pair_row_start(i, n));
+}
+
+// ---- one offset: G (T, n, 3) and per-(frame, site block) energy partials.  Thread = (frame, site i); a workgroup
+// holds `fpb` frames x `iblk` sites (n <= 256: whole frames, 256 / n of them; else 1 frame x 256 sites) and stages
+// the j sites of its frames in LDS, MV_JT at a time.
+template <typename TX>
+__global__ __launch_bounds__(MV_THREADS) void gauss_site_forces_kernel(const TX* __restrict__ X, int64_t T, int32_t n,
+                                                                        int32_t fpb, int32_t iblk, int32_t n_iblk,
+                                                                        int64_t n_blocks, TX offset, TX k, double scale,
+                                                                        TX* __restrict__ G, double* __restrict__ eslab) {
+  __shared__ TX sx[MV_JT * 3];
+  __shared__ double se[MV_THREADS];
+  const int tid = threadIdx.x;
+  const int f = tid / iblk, il = tid - f * iblk;
+  for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    const int64_t tb = b / n_iblk;
+    const int ib = (int)(b - tb * n_iblk);
+    const int64_t t0 = tb * fpb;
+    const int nf = (int)(T - t0 < fpb ? T - t0 : fpb);
+    const int64_t i = (int64_t)ib * iblk + il;
+    const bool active = f < nf && il < iblk && i < n;
+    const int64_t t = t0 + f;
+    TX r0 = 0, r1 = 0, r2 = 0;
+    if (active) {
+      const TX* xi = X + (t * n + i) * 3;
+      r0 = xi[0];
+      r1 = xi[1];
+      r2 = xi[2];
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, e = 0.0;
+    for (int64_t j0 = 0; j0 < n; j0 += MV_JT) {
+      const int jn = (int)(n - j0 < MV_JT ? n - j0 : MV_JT);
+      __syncthreads();
+      for (int m = tid; m < nf * jn * 3; m += MV_THREADS) {
+        const int ff = m / (jn * 3), q = m - ff * (jn * 3);
+        sx[m] = X[((t0 + ff) * n + j0) * 3 + q];
+      }
+      __syncthreads();
+      if (active) {
+        const TX* base = sx + f * jn * 3;
+        for (int j = 0; j < jn; ++j) {
+          const TX d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
+          const TX tt = sq_norm3(d0, d1, d2) - offset;
+          const TX g = Gauss<TX>::g(tt, k);
+          const double c = (double)(tt * g);
+          a0 += c * (double)d0;
+          a1 += c * (double)d1;
+          a2 += c * (double)d2;
+          e += (double)g;
+        }
+      }
+    }
+    if (G && active) {
+      TX* gi = G + (t * n + i) * 3;
+      gi[0] = (TX)(scale * a0);
+      gi[1] = (TX)(scale * a1);
+      gi[2] = (TX)(scale * a2);
+    }
+    if (eslab) {
+      se[tid] = active ? e : 0.0;
+      __syncthreads();
+      if (tid < nf) {
+        double s = 0.0;
+        for (int l = 0; l < iblk; ++l) s += se[tid * iblk + l];
+        eslab[(t0 + tid) * n_iblk + ib] = s;
+      }
+    }
+  }
+}
+
+// E[t] = sum_ib eslab[t][ib], in order
+template <typename TX>
+__global__ __launch_bounds__(256) void gauss_energy_finish_kernel(const double* __restrict__ eslab, int64_t T,
+                                                                  int32_t n_iblk, TX* __restrict__ E) {
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (int64_t)gridDim.x * 256) {
+    double s = 0.0;
+    for (int ib = 0; ib < n_iblk; ++ib) s += eslab[t * n_iblk + ib];
+    E[t] = (TX)s;
+  }
+}
+
+// ---- S offsets, projection, pair form.  Grid (K splits of the T * n (n - 1) / 2 entries, offset chunks).
+// slabs[k][s] = sum over split k of (x - o_s) g_s(x) u.
+template <typename TX, typename TF>
+__global__ __launch_bounds__(MV_THREADS) void gauss_proj_kernel(const TX* __restrict__ X, const TF* __restrict__ F,
+                                                                 int64_t T, int32_t n,
+                                                                 const double* __restrict__ offsets, int64_t S,
+                                                                 double width, int64_t per_split,
+                                                                 double* __restrict__ slabs) {
+  typedef typename Promote<TX, TF>::type C;
+  __shared__ C sx[MV_PL], su[MV_PL];
+  const int tid = threadIdx.x;
+  const int64_t P = (int64_t)n * (n - 1) / 2, n_entries = T * P;
+  const int64_t e_begin = (int64_t)blockIdx.x * per_split;
+  const int64_t e_end = e_begin + per_split < n_entries ? e_begin + per_split : n_entries;
+  const int64_t s0 = (int64_t)blockIdx.y * MV_SCHUNK + tid;
+  const C k = Gauss<C>::coef(width);
+  C off[MV_SC];
+  double acc[MV_SC];
+#pragma unroll
+  for (int q = 0; q < MV_SC; ++q) {
+    const int64_t s = s0 + (int64_t)q * MV_THREADS;
+    off[q] = s < S ? (C)offsets[s] : (C)0;
+    acc[q] = 0.0;
+  }
+  for (int64_t e0 = e_begin; e0 < e_end; e0 += MV_PL) {
+    const int ne = (int)(e_end - e0 < MV_PL ? e_end - e0 : MV_PL);
+    __syncthreads();
+    for (int m = tid; m < ne; m += MV_THREADS) {
+      const int64_t e = e0 + m, t = e / P;
+      int64_t i, j;
+      pair_of(e - t * P, n, &i, &j);
+      const TX* xi = X + (t * n + i) * 3;
+      const TX* xj = X + (t * n + j) * 3;
+      const TF* fi = F + (t * n + i) * 3;
+      const TF* fj = F + (t * n + j) * 3;
+      const C d0 = (C)xi[0] - (C)xj[0], d1 = (C)xi[1] - (C)xj[1], d2 = (C)xi[2] - (C)xj[2];
+      sx[m] = sq_norm3(d0, d1, d2);
+      su[m] = d0 * ((C)fi[0] - (C)fj[0]) + d1 * ((C)fi[1] - (C)fj[1]) + d2 * ((C)fi[2] - (C)fj[2]);
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int m = 0; m < ne; ++m) {
+      const C x = sx[m], u = su[m];
+#pragma unroll
+      for (int q = 0; q < MV_SC; ++q) {
+        const C tt = x - off[q];
+        acc[q] += (double)(tt * Gauss<C>::g(tt, k) * u);
+      }
+    }
+  }
+  double* slab = slabs + (int64_t)blockIdx.x * S;
+#pragma unroll
+  for (int q = 0; q < MV_SC; ++q) {
+    const int64_t s = s0 + (int64_t)q * MV_THREADS;
+    if (s < S) slab[s] = acc[q];
+  }
+}
+
+// ---- S offsets, residual shift, per-site form.  Grid (K splits of the frames, offset chunks).
+// slabs[k][s][0] = sum F_i . G~_s,i, slabs[k][s][1] = sum |G~_s,i|^2 over split k's frames, G~ = G w^2 / 8.
+template <typename TX, typename TF>
+__global__ __launch_bounds__(MV_THREADS) void gauss_shift_kernel(const TX* __restrict__ X, const TF* __restrict__ F,
+                                                                  int64_t T, int32_t n,
+                                                                  const double* __restrict__ offsets, int64_t S,
+                                                                  double width, int64_t frames_per_split,
+                                                                  double* __restrict__ slabs) {
+  typedef typename Promote<TX, TF>::type C;
+  __shared__ C sx[MV_JT * 3];
+  const int tid = threadIdx.x;
+  const int64_t t_begin = (int64_t)blockIdx.x * frames_per_split;
+  const int64_t t_end = t_begin + frames_per_split < T ? t_begin + frames_per_split : T;
+  const int64_t s0 = (int64_t)blockIdx.y * MV_SCHUNK + tid;
+  const C k = Gauss<C>::coef(width);
+  C off[MV_SC];
+  double ip[MV_SC], gs[MV_SC];
+#pragma unroll
+  for (int q = 0; q < MV_SC; ++q) {
+    const int64_t s = s0 + (int64_t)q * MV_THREADS;
+    off[q] = s < S ? (C)offsets[s] : (C)0;
+    ip[q] = gs[q] = 0.0;
+  }
+  const bool whole = n <= MV_JT;      // whole frames in LDS, MV_JT / n of them per stage
+  const int fb = whole ? MV_JT / n : 1;
+  for (int64_t t0 = t_begin; t0 < t_end; t0 += fb) {
+    const int nf = (int)(t_end - t0 < fb ? t_end - t0 : fb);
+    if (whole) {
+      __syncthreads();
+      const TX* src = X + t0 * n * 3;
+      for (int m = tid; m < nf * n * 3; m += MV_THREADS) sx[m] = (C)src[m];
+      __syncthreads();
+    }
+    for (int f = 0; f < nf; ++f) {
+      const int64_t t = t0 + f;
+      for (int64_t i = 0; i < n; ++i) {
+        const TX* xi = X + (t * n + i) * 3;
+        const TF* fi = F + (t * n + i) * 3;
+        C r0, r1, r2;
+        if (whole) {
+          r0 = sx[(f * n + i) * 3];
+          r1 = sx[(f * n + i) * 3 + 1];
+          r2 = sx[(f * n + i) * 3 + 2];
+        } else {
+          r0 = (C)xi[0];
+          r1 = (C)xi[1];
+          r2 = (C)xi[2];
+        }
+        double g[MV_SC][3];
+#pragma unroll
+        for (int q = 0; q < MV_SC; ++q) g[q][0] = g[q][1] = g[q][2] = 0.0;
+        for (int64_t j0 = 0; j0 < n; j0 += MV_JT) {
+          const int jn = (int)(n - j0 < MV_JT ? n - j0 : MV_JT);
+          const C* base = sx + (whole ? f * n * 3 : 0);
+          if (!whole) {
+            __syncthreads();
+            const TX* src = X + (t * n + j0) * 3;
+            for (int m = tid; m < jn * 3; m += MV_THREADS) sx[m] = (C)src[m];
+            __syncthreads();
+          }
+          for (int j = 0; j < jn; ++j) {
+            const C d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
+            const C x = sq_norm3(d0, d1, d2);
+            const double e0 = (double)d0, e1 = (double)d1, e2 = (double)d2;
+#pragma unroll
+            for (int q = 0; q < MV_SC; ++q) {
+              const C tt = x - off[q];
+              const double c = (double)(tt * Gauss<C>::g(tt, k));
+              g[q][0] += c * e0;
+              g[q][1] += c * e1;
+              g[q][2] += c * e2;
+            }
+          }
+        }
+        const double f0 = (double)fi[0], f1 = (double)fi[1], f2 = (double)fi[2];
+#pragma unroll
+        for (int q = 0; q < MV_SC; ++q) {
+          ip[q] += f0 * g[q][0] + f1 * g[q][1] + f2 * g[q][2];
+          gs[q] += g[q][0] * g[q][0] + g[q][1] * g[q][1] + g[q][2] * g[q][2];
+        }
+      }
+    }
+  }
+  double* slab = slabs + (int64_t)blockIdx.x * S * 2;
+#pragma unroll
+  for (int q = 0; q < MV_SC; ++q) {
+    const int64_t s = s0 + (int64_t)q * MV_THREADS;
+    if (s < S) {
+      slab[2 * s] = ip[q];
+      slab[2 * s + 1] = gs[q];
+    }
+  }
+}
+
+// out_w[s] = scale_w * sum_k slabs[k][s][w] (w < W), k ascending
+__global__ __launch_bounds__(256) void mapval_slab_reduce_kernel(const double* __restrict__ slabs, int64_t K, int64_t S,
+                                                                 int W, double scale0, double scale1,
+                                                                 double* __restrict__ out0, double* __restrict__ out1) {
+  for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < S; s += (int64_t)gridDim.x * 256) {
+    double a = 0.0, b = 0.0;
+    for (int64_t k = 0; k < K; ++k) {
+      a += slabs[(k * S + s) * W];
+      if (W == 2) b += slabs[(k * S + s) * W + 1];
+    }
+    out0[s] = scale0 * a;
+    if (W == 2) out1[s] = scale1 * b;
+  }
+}
+
+// ---- fixed-order dot product: workgroup w takes elements w*256 + tid + m * (MV_DOT_BLOCKS * 256), four accumulators
+template <typename TA, typename TB>
+__global__ __launch_bounds__(256) void dot_kernel(const TA* __restrict__ a, const TB* __restrict__ b, int64_t n,
+                                                  double* __restrict__ partials) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (; i + 3 * stride < n; i += 4 * stride) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] += (double)a[i + u * stride] * (double)b[i + u * stride];
+  }
+  for (; i < n; i += stride) acc[0] += (double)a[i] * (double)b[i];
+  double s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  __shared__ double w[4];
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (w[0] + w[1]) + (w[2] + w[3]);
+}
+
+__global__ __launch_bounds__(256) void dot_finish_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  __shared__ double w[4];
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (w[0] + w[1]) + (w[2] + w[3]);
+}
+
+// ---- host: shapes and launch plans
+static bool mv_dtype_ok(int d) { return d == AGGF_F32 || d == AGGF_F64; }
+
+// T * n * n fits in int64 with room (every index of the kernels is below it)
+static bool mv_shape_ok(int64_t T, int32_t n) {
+  if (T <= 0 || n <= 0) return false;
+  return T <= ((int64_t)1 << 60) / ((int64_t)n * n);
+}
+
+struct SitePlan {
+  int32_t fpb, iblk, n_iblk;
+  int64_t n_blocks;
+};
+static SitePlan site_plan(int64_t T, int32_t n) {
+  SitePlan p;
+  p.fpb = n <= MV_THREADS ? MV_THREADS / n : 1;
+  p.iblk = n <= MV_THREADS ? n : MV_THREADS;
+  p.n_iblk = (int32_t)ceil_div(n, p.iblk);
+  p.n_blocks = ceil_div(T, p.fpb) * p.n_iblk;
+  return p;
+}
+
+struct SplitPlan {
+  int64_t K, per_split, n_sch;
+};
+// split `units` (pair entries or frames) into K ranges; at least `min_units` per range
+static SplitPlan split_plan(int64_t units, int64_t min_units, int64_t S, int W) {
+  SplitPlan p;
+  p.n_sch = ceil_div(S, MV_SCHUNK);
+  int64_t k = ceil_div(MV_TARGET_WGS, p.n_sch);
+  const int64_t k_units = ceil_div(units, min_units);
+  if (k > k_units) k = k_units;
+  const int64_t k_mem = MV_SLAB_MAX / (S * W);
+  if (k > k_mem) k = k_mem;
+  if (k < 1) k = 1;
+  p.per_split = units > 0 ? ceil_div(units, k) : 1;
+  p.K = units > 0 ? ceil_div(units, p.per_split) : 1;
+  return p;
+}
+
+static bool mv_samples_ok(int64_t S) { return S > 0 && ceil_div(S, MV_SCHUNK) <= 65535; }
+
+static size_t proj_ws(int64_t T, int32_t n, int64_t S) {
+  const SplitPlan p = split_plan(T * ((int64_t)n * (n - 1) / 2), MV_PL, S, 1);
+  return (size_t)(p.K * S) * sizeof(double) + 256;
+}
+static size_t shift_ws(int64_t T, int64_t S) {
+  const SplitPlan p = split_plan(T, 1, S, 2);
+  return (size_t)(p.K * S * 2) * sizeof(double) + 256;
+}
+
+}  // namespace aggf
+
+using namespace aggf;
+
+extern "C" size_t aggf_gauss_pair_forces_workspace_bytes(int64_t T, int32_t n) {
+  if (!mv_shape_ok(T, n)) return 0;
+  const SitePlan p = site_plan(T, n);
+  return (size_t)(T * p.n_iblk) * sizeof(double) + 256;
+}
+
+extern "C" int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
+                                      void* G, void* E, void* ws, size_t ws_bytes, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (!X || (!G && !E)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: NULL pointer");
+  if (!mv_dtype_ok(dtype)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: bad dtype");
+  if (!mv_shape_ok(T, n)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: bad shape (T=%lld, n=%d)", (long long)T, n);
+  if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: width must be positive");
+  const SitePlan p = site_plan(T, n);
+  double* eslab = nullptr;
+  if (E) {
+    if (!ws) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: NULL workspace");
+    if (ws_bytes < (size_t)(T * p.n_iblk) * sizeof(double))
+      return fail(AGGF_ERR_WORKSPACE, "aggf_gauss_pair_forces: workspace too small");
+    eslab = (double*)ws;
+  }
+  const dim3 grid((unsigned)(p.n_blocks < MV_MAX_GRID ? p.n_blocks : MV_MAX_GRID));
+  const double scale = 8.0 / (width * width);
+  const int64_t fg = ceil_div(T, 256) < 4096 ? ceil_div(T, 256) : 4096;
+  if (dtype == AGGF_F64) {
+    AGGF_LAUNCH(gauss_site_forces_kernel<double>, grid, dim3(MV_THREADS), 0, stream, (const double*)X, T, n, p.fpb,
+                p.iblk, p.n_iblk, p.n_blocks, offset, Gauss<double>::coef(width), scale, (double*)G, eslab);
+    AGGF_LAUNCH_OK();
+    if (E) AGGF_LAUNCH(gauss_energy_finish_kernel<double>, dim3((unsigned)fg), dim3(256), 0, stream, eslab, T, p.n_iblk,
+                       (double*)E);
+  } else {
+    AGGF_LAUNCH(gauss_site_forces_kernel<float>, grid, dim3(MV_THREADS), 0, stream, (const float*)X, T, n, p.fpb,
+                p.iblk, p.n_iblk, p.n_blocks, (float)offset, Gauss<float>::coef(width), scale, (float*)G, eslab);
+    AGGF_LAUNCH_OK();
+    if (E) AGGF_LAUNCH(gauss_energy_finish_kernel<float>, dim3((unsigned)fg), dim3(256), 0, stream, eslab, T, p.n_iblk,
+                       (float*)E);
+  }
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+extern "C" size_t aggf_gauss_proj_workspace_bytes(int64_t T, int32_t n, int64_t S) {
+  if (!mv_shape_ok(T, n) || !mv_samples_ok(S)) return 0;
+  return proj_ws(T, n, S);
+}
+
+extern "C" size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t S) {
+  if (!mv_shape_ok(T, n) || !mv_samples_ok(S)) return 0;
+  return shift_ws(T, S);
+}
+
+template <typename TX>
+static void launch_proj_x(const TX* X, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets,
+                          int64_t S, double width, const SplitPlan& p, double* slabs, hipStream_t stream) {
+  const dim3 grid((unsigned)p.K, (unsigned)p.n_sch);
+  if (f_dtype == AGGF_F64)
+    AGGF_LAUNCH((gauss_proj_kernel<TX, double>), grid, dim3(MV_THREADS), 0, stream, X, (const double*)F, T, n, offsets,
+                S, width, p.per_split, slabs);
+  else
+    AGGF_LAUNCH((gauss_proj_kernel<TX, float>), grid, dim3(MV_THREADS), 0, stream, X, (const float*)F, T, n, offsets,
+                S, width, p.per_split, slabs);
+}
+
+template <typename TX>
+static void launch_shift_x(const TX* X, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets,
+                           int64_t S, double width, const SplitPlan& p, double* slabs, hipStream_t stream) {
+  const dim3 grid((unsigned)p.K, (unsigned)p.n_sch);
+  if (f_dtype == AGGF_F64)
+    AGGF_LAUNCH((gauss_shift_kernel<TX, double>), grid, dim3(MV_THREADS), 0, stream, X, (const double*)F, T, n,
+                offsets, S, width, p.per_split, slabs);
+  else
+    AGGF_LAUNCH((gauss_shift_kernel<TX, float>), grid, dim3(MV_THREADS), 0, stream, X, (const float*)F, T, n, offsets,
+                S, width, p.per_split, slabs);
+}
+
+static int mv_check(const char* who, const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                    const double* offsets, int64_t S, double width, const void* out0, const void* out1, const void* ws,
+                    size_t ws_bytes, size_t need) {
+  if (!X || !F || !offsets || !out0 || !out1 || !ws) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if (!mv_dtype_ok(x_dtype) || !mv_dtype_ok(f_dtype)) return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
+  if (!mv_shape_ok(T, n)) return fail(AGGF_ERR_ARG, "%s: bad shape (T=%lld, n=%d)", who, (long long)T, n);
+  if (!mv_samples_ok(S)) return fail(AGGF_ERR_ARG, "%s: bad sample count %lld", who, (long long)S);
+  if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "%s: width must be positive", who);
+  if (ws_bytes < need - 256) return fail(AGGF_ERR_WORKSPACE, "%s: workspace too small", who);
+  return AGGF_OK;
+}
+
+extern "C" int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                               const double* offsets, int64_t S, double width, double* out, void* ws, size_t ws_bytes,
+                               void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  const size_t need = mv_shape_ok(T, n) && mv_samples_ok(S) ? proj_ws(T, n, S) : 256;
+  const int rc = mv_check("aggf_gauss_proj", X, x_dtype, F, f_dtype, T, n, offsets, S, width, out, out, ws, ws_bytes,
+                          need);
+  if (rc != AGGF_OK) return rc;
+  const SplitPlan p = split_plan(T * ((int64_t)n * (n - 1) / 2), MV_PL, S, 1);
+  double* slabs = (double*)ws;
+  if (x_dtype == AGGF_F64)
+    launch_proj_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+  else
+    launch_proj_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+  AGGF_LAUNCH_OK();
+  const int64_t g = ceil_div(S, 256) < 1024 ? ceil_div(S, 256) : 1024;
+  AGGF_LAUNCH(mapval_slab_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, slabs, p.K, S, 1,
+              8.0 / (width * width), 0.0, out, (double*)nullptr);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+extern "C" int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                                const double* offsets, int64_t S, double width, double* ip, double* gsq, void* ws,
+                                size_t ws_bytes, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  const size_t need = mv_shape_ok(T, n) && mv_samples_ok(S) ? shift_ws(T, S) : 256;
+  const int rc = mv_check("aggf_gauss_shift", X, x_dtype, F, f_dtype, T, n, offsets, S, width, ip, gsq, ws, ws_bytes,
+                          need);
+  if (rc != AGGF_OK) return rc;
+  const SplitPlan p = split_plan(T, 1, S, 2);
+  double* slabs = (double*)ws;
+  if (x_dtype == AGGF_F64)
+    launch_shift_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+  else
+    launch_shift_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+  AGGF_LAUNCH_OK();
+  const double sc = 8.0 / (width * width);
+  const int64_t g = ceil_div(S, 256) < 1024 ? ceil_div(S, 256) : 1024;
+  AGGF_LAUNCH(mapval_slab_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, slabs, p.K, S, 2, sc, sc * sc, ip,
+              gsq);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+extern "C" size_t aggf_dot_workspace_bytes(void) { return MV_DOT_BLOCKS * sizeof(double); }
+
+extern "C" int aggf_dot(const void* a, int a_dtype, const void* b, int b_dtype, int64_t count, double* out, void* ws,
+                        size_t ws_bytes, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (!a || !b || !out || !ws) return fail(AGGF_ERR_ARG, "aggf_dot: NULL pointer");
+  if (!mv_dtype_ok(a_dtype) || !mv_dtype_ok(b_dtype)) return fail(AGGF_ERR_ARG, "aggf_dot: bad dtype");
+  if (count < 0) return fail(AGGF_ERR_ARG, "aggf_dot: negative count");
+  if (ws_bytes < MV_DOT_BLOCKS * sizeof(double)) return fail(AGGF_ERR_WORKSPACE, "aggf_dot: workspace too small");
+  double* part = (double*)ws;
+  const dim3 grid(MV_DOT_BLOCKS);
+  if (a_dtype == AGGF_F64 && b_dtype == AGGF_F64)
+    AGGF_LAUNCH((dot_kernel<double, double>), grid, dim3(256), 0, stream, (const double*)a, (const double*)b, count, part);
+  else if (a_dtype == AGGF_F64)
+    AGGF_LAUNCH((dot_kernel<double, float>), grid, dim3(256), 0, stream, (const double*)a, (const float*)b, count, part);
+  else if (b_dtype == AGGF_F64)
+    AGGF_LAUNCH((dot_kernel<float, double>), grid, dim3(256), 0, stream, (const float*)a, (const double*)b, count, part);
+  else
+    AGGF_LAUNCH((dot_kernel<float, float>), grid, dim3(256), 0, stream, (const float*)a, (const float*)b, count, part);
+  AGGF_LAUNCH_OK();
+  AGGF_LAUNCH(dot_finish_kernel, dim3(1), dim3(256), 0, stream, part, MV_DOT_BLOCKS, out);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}

@@ -1,5 +1,5 @@
 // Host-side sanitizer harness of the C ABI (`make asan`, CPU box, no GPU needed): libaggf's HOST code -- argument
-// validation, launch planning, the hand-computed workspace layouts of its 62 entry points -- built with
+// validation, launch planning, the hand-computed workspace layouts of its entry points -- built with
 // -fsanitize=address,undefined (host pass only: the kernels are not compiled) and driven through
 //   * every *_workspace_bytes query over a grid of shapes (empty, tiny, ragged, BASELINE-sized, absurd),
 //   * every compute entry with NULL pointers and with bad shapes / dtypes: must refuse with an error code,
@@ -60,6 +60,11 @@ int main() {
       sink += aggf_linearmap_apply_workspace_bytes(T, N, N / 16 + 1);
       sink += aggf_gram_pair_workspace_bytes(T, N, 128, AGGF_F64);
       sink += aggf_pair_dist_var_workspace_bytes(T, N);
+      sink += aggf_gauss_pair_forces_workspace_bytes(T, N);
+      for (int64_t S : {(int64_t)0, (int64_t)1, (int64_t)37, (int64_t)1000, (int64_t)1 << 26, (int64_t)1 << 40}) {
+        sink += aggf_gauss_proj_workspace_bytes(T, N, S);
+        sink += aggf_gauss_shift_workspace_bytes(T, N, S);
+      }
     }
   for (int32_t n : Ns)
     for (int32_t m : {0, 1, 10, 64, 256, 1300}) {
@@ -70,6 +75,7 @@ int main() {
       sink += aggf_gram_quadform_workspace_bytes(n, m);
     }
   sink += aggf_sumsq_workspace_bytes();
+  sink += aggf_dot_workspace_bytes();
   printf("workspace queries done (checksum %zu)\n", sink);
 
   // ---- NULL pointers / bad shapes must be refused
@@ -132,6 +138,42 @@ int main() {
   REFUSED(aggf_feat_weights(nullptr, 0, 10, 5, 7, d, 10, d, nullptr));
   REFUSED(aggf_pair_dist_var(nullptr, 10, 5, 1, d, ws, WS, nullptr));
   REFUSED(aggf_pair_dist_moments(p, 10, 5, 1, nullptr, d, ws, WS, nullptr));
+  // K7: NULL pointers, bad shapes / dtypes / sample counts, widths that are not positive, short workspaces
+  REFUSED(aggf_gauss_pair_forces(nullptr, 10, 5, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, nullptr, ws, WS, nullptr));  // neither G nor E
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, p, nullptr, WS, nullptr));  // E without workspace
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, p, ws, 8, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 0, 5, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 0, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, (int64_t)1 << 40, 20000, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 2, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, -1.0, p, nullptr, ws, WS, nullptr));
+  for (int shift = 0; shift < 2; ++shift) {
+    auto call = [&](const void* X, int xd, const void* F, int fd, int64_t T, int32_t n, const double* o, int64_t S,
+                    double w, double* out, size_t wsb) {
+      return shift ? aggf_gauss_shift(X, xd, F, fd, T, n, o, S, w, out, out ? d + 4096 : nullptr, ws, wsb, nullptr)
+                   : aggf_gauss_proj(X, xd, F, fd, T, n, o, S, w, out, ws, wsb, nullptr);
+    };
+    REFUSED(call(nullptr, 1, p, 1, 10, 5, d, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, nullptr, 1, 10, 5, d, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, 5, nullptr, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, 5, d, 4, 0.5, nullptr, WS));
+    REFUSED(call(p, 3, p, 1, 10, 5, d, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, p, -1, 10, 5, d, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, -1, 5, d, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, -5, d, 4, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, 5, d, 0, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, 5, d, (int64_t)1 << 40, 0.5, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, 5, d, 4, 0.0, d, WS));
+    REFUSED(call(p, 1, p, 1, 10, 5, d, 4, __builtin_nan(""), d, WS));
+    REFUSED(call(p, 1, p, 1, 100000, 256, d, 1000, 0.5, d, 64));
+  }
+  REFUSED(aggf_dot(nullptr, 1, p, 1, 10, d, ws, WS, nullptr));
+  REFUSED(aggf_dot(p, 1, p, 1, 10, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_dot(p, 1, p, 7, 10, d, ws, WS, nullptr));
+  REFUSED(aggf_dot(p, 1, p, 1, -1, d, ws, WS, nullptr));
+  REFUSED(aggf_dot(p, 1, p, 1, 10, d, ws, 8, nullptr));
   REFUSED(aggf_pair_pool_term(nullptr, d, d, 1.0, 10, d, nullptr));
   REFUSED(aggf_gram_quadform(nullptr, 10, d, 2, d, ws, WS, nullptr));
   REFUSED(aggf_daxpby(10, 1.0, nullptr, 1.0, d, d, nullptr));
@@ -195,6 +237,23 @@ int main() {
     RUNS(aggf_not_close(p, (char*)p + 4096, 1000, 1, 1e-5, 1e-6, i32, nullptr));
     RUNS(aggf_daxpby(1000, 1.0, d, -1.0, d + 1000, d + 2000, nullptr));
   }
+  // K7 with plausible arguments and the queried workspace: every dtype pair, few and many sites, few and many samples
+  for (int64_t T : {(int64_t)1, (int64_t)7, (int64_t)100000})
+    for (int32_t n : {1, 2, 10, 256, 1025, 4096})
+      for (int64_t S : {(int64_t)1, (int64_t)37, (int64_t)1000, (int64_t)70000}) {
+        const size_t wf = aggf_gauss_pair_forces_workspace_bytes(T, n);
+        const size_t wpj = aggf_gauss_proj_workspace_bytes(T, n, S), wsh = aggf_gauss_shift_workspace_bytes(T, n, S);
+        for (int xd = 0; xd < 2; ++xd)
+          for (int fd = 0; fd < 2; ++fd) {
+            if (fd == 0 && S == 1) {
+              if (wf <= WS) RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, p, (char*)p + 4096, ws, wf, nullptr));
+              RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, p, nullptr, nullptr, 0, nullptr));
+            }
+            if (wpj <= WS) RUNS(aggf_gauss_proj(p, xd, p, fd, T, n, d, S, 0.25, d + 4096, ws, wpj, nullptr));
+            if (wsh <= WS) RUNS(aggf_gauss_shift(p, xd, p, fd, T, n, d, S, 0.25, d + 4096, d + 8192, ws, wsh, nullptr));
+            RUNS(aggf_dot(p, xd, (char*)p + 4096, fd, T * n * 3, d, ws, aggf_dot_workspace_bytes(), nullptr));
+          }
+      }
   free(raw);
   printf("%d calls, %d unexpected statuses\n", n_calls, n_bad);
   return n_bad ? 1 : 0;

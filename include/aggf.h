@@ -506,6 +506,40 @@ int aggf_concat_sites(const void* a, int32_t Na, int a_dtype, const void* b, int
 int aggf_scale(const void* x, int64_t count, int dtype, double alpha, void* out, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K7  Map validation with random Gaussian pair-potential force fields.
+ *
+ * Replaces jaxmapval.py:79-131 (rsqpg_forces), 159-237 (random_residual_shift), 266-319 (random_force_proj),
+ * 322-360 (mscg_ip) and 365-401 (sq_gaussian_energies / sq_gaussian_forces).  One Gaussian of the squared pair
+ * distance, g(x) = exp(-((x - o) / w)^2), x = |r_i - r_j|^2, summed over the full n x n matrix of a frame:
+ *     E_t = sum_{i,j} g(x_ij)   (the diagonal adds n exp(-(o / w)^2)),
+ *     G_i = -dE/dr_i = (8 / w^2) sum_j (x_ij - o) g(x_ij) (r_i - r_j).
+ * X (coordinates) and F (forces): (T, n, 3), each AGGF_F32 or AGGF_F64 independently.  Arithmetic is float64
+ * when either input is float64, float32 (hardware exp) when both are float32; every sum is float64, partial sums go
+ * to slabs in the caller's workspace and are combined in a fixed order (bit-identical run to run).  x is formed
+ * from the differences r_i - r_j.  width must be positive (the reference returns NaN / inf otherwise); NaN inputs
+ * propagate.  offsets[S] are float64 device values.
+ *   aggf_gauss_pair_forces  one offset: G (T, n, 3) and / or E (T,) (either may be NULL, not both), both in `dtype`;
+ *                           the workspace is needed for E only;
+ *   aggf_gauss_proj         out[s] = sum_t sum_i F[t,i] . G_s[t,i]   (mscg_ip of sample s is out[s] / T);
+ *   aggf_gauss_shift        ip[s] = sum_t sum_i F[t,i] . G_s[t,i], gsq[s] = sum_t sum_i |G_s[t,i]|^2 in one pass
+ *                           (the residual shift of sample s is (gsq[s] - 2 ip[s]) / (3 n T));
+ *   aggf_dot                out[0] = sum a[k] b[k] over `count` elements (mscg_ip and the generic sample loop).
+ * ------------------------------------------------------------------------- */
+size_t aggf_gauss_pair_forces_workspace_bytes(int64_t T, int32_t n);
+int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width, void* G,
+                           void* E, void* ws, size_t ws_bytes, void* stream);
+size_t aggf_gauss_proj_workspace_bytes(int64_t T, int32_t n, int64_t S);
+int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets,
+                    int64_t S, double width, double* out, void* ws, size_t ws_bytes, void* stream);
+size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t S);
+int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                     const double* offsets, int64_t S, double width, double* ip, double* gsq, void* ws,
+                     size_t ws_bytes, void* stream);
+size_t aggf_dot_workspace_bytes(void);
+int aggf_dot(const void* a, int a_dtype, const void* b, int b_dtype, int64_t count, double* out, void* ws,
+             size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Synthetic trajectories for benchmarks and full-size property tests (no
  * reference counterpart).  out[t,a,d] = mean + sigma * z(seed, frame_offset+t, a, d)
  * with z a counter-based standard normal (Philox4x32-10 + Box-Muller), so any
