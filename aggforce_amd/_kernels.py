@@ -1088,3 +1088,62 @@ def dot(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     check(l.aggf_dot(ptr(a), dtype_code(a.dtype), ptr(b), dtype_code(b.dtype), a.numel(), ptr(out), ptr(ws), need,
                      stream_ptr()), "aggf_dot")
     return out
+
+
+# ------------------------------------------------------------------ K8 backward contractions (aggforce_amd/_autograd.py)
+
+
+def trjdot_cross(a: torch.Tensor, b: torch.Tensor, out_dtype: torch.dtype, out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False) -> torch.Tensor:
+    """(n_a, n_b) in out_dtype: sum over frames and dimensions of a[t,i,d] b[t,j,d] (aggf_trjdot_cross; ``accumulate``
+    adds to ``out``).  a and b must share a dtype: widen one of them first."""
+    l = lib()
+    T, n_a, _ = a.shape
+    n_b = b.shape[1]
+    if a.dtype != b.dtype or tuple(b.shape) != (T, n_b, 3) or a.shape[2] != 3:
+        raise ValueError(f"trjdot_cross: operands {tuple(a.shape)} {a.dtype}, {tuple(b.shape)} {b.dtype}")
+    if out is None:
+        out = (torch.zeros if accumulate else torch.empty)((n_a, n_b), dtype=out_dtype, device=a.device)
+    if T == 0 or n_a == 0 or n_b == 0:
+        if not accumulate:
+            out.zero_()
+        return out
+    need = l.aggf_trjdot_cross_workspace_bytes(T, n_a, n_b, dtype_code(a.dtype))
+    ws = workspace(need, a.device, "trjgrad")
+    with _timed("trjdot_cross"):
+        check(l.aggf_trjdot_cross(ptr(a), ptr(b), T, n_a, n_b, dtype_code(a.dtype), ptr(out), dtype_code(out.dtype),
+                                  int(accumulate), ptr(ws), need, stream_ptr()), "aggf_trjdot_cross")
+    return out
+
+
+def trjdot_frames_t(g: torch.Tensor, f: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """out[t,a,d] = sum_c f[t,c,a] g[t,c,d] -> (T, N, 3) in out_dtype (aggf_trjdot_frames_t); g and f share a dtype
+    at least as wide as out_dtype."""
+    T, n_cg, N = f.shape
+    if tuple(g.shape) != (T, n_cg, 3) or g.dtype != f.dtype:
+        raise ValueError(f"trjdot_frames_t: operands {tuple(g.shape)} {g.dtype}, {tuple(f.shape)} {f.dtype}")
+    out = torch.empty((T, N, 3), dtype=out_dtype, device=g.device)
+    if n_cg == 0:
+        return out.zero_()
+    if T == 0 or N == 0:
+        return out
+    with _timed("trjdot_frames_t"):
+        check(lib().aggf_trjdot_frames_t(ptr(g), ptr(f), dtype_code(g.dtype), T, n_cg, N, ptr(out),
+                                         dtype_code(out_dtype), stream_ptr()), "aggf_trjdot_frames_t")
+    return out
+
+
+def trjdot_frames_outer(g: torch.Tensor, p: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """out[t,c,a] = sum_d g[t,c,d] p[t,a,d] -> (T, n_cg, N) in out_dtype (aggf_trjdot_frames_outer); g and p share a
+    dtype at least as wide as out_dtype."""
+    T, n_cg, _ = g.shape
+    N = p.shape[1]
+    if tuple(p.shape) != (T, N, 3) or g.shape[2] != 3 or g.dtype != p.dtype:
+        raise ValueError(f"trjdot_frames_outer: operands {tuple(g.shape)} {g.dtype}, {tuple(p.shape)} {p.dtype}")
+    out = torch.empty((T, n_cg, N), dtype=out_dtype, device=g.device)
+    if T == 0 or n_cg == 0 or N == 0:
+        return out
+    with _timed("trjdot_frames_outer"):
+        check(lib().aggf_trjdot_frames_outer(ptr(g), ptr(p), dtype_code(g.dtype), T, n_cg, N, ptr(out),
+                                             dtype_code(out_dtype), stream_ptr()), "aggf_trjdot_frames_outer")
+    return out

@@ -254,6 +254,30 @@ int main() {
             RUNS(aggf_dot(p, xd, (char*)p + 4096, fd, T * n * 3, d, ws, aggf_dot_workspace_bytes(), nullptr));
           }
       }
+  // K8: the workspace query over a grid of shapes, refusals, and plausible calls with the queried workspace
+  for (int64_t T : Ts)
+    for (int32_t N : Ns) sink += aggf_trjdot_cross_workspace_bytes(T, N / 16 + 1, N, 1) + aggf_trjdot_cross_workspace_bytes(T, N, N, 0);
+  REFUSED(aggf_trjdot_cross(nullptr, p, 7, 3, 5, 1, d, 1, 0, ws, WS, nullptr));
+  REFUSED(aggf_trjdot_cross(p, p, 0, 3, 5, 1, d, 1, 0, ws, WS, nullptr));
+  REFUSED(aggf_trjdot_cross(p, p, 7, 3, 5, 2, d, 1, 0, ws, WS, nullptr));
+  REFUSED(aggf_trjdot_cross(p, p, 7, 3, 5, 1, d, 1, 0, ws, 0, nullptr));
+  REFUSED(aggf_trjdot_frames_t(p, nullptr, 1, 7, 3, 5, d, 1, nullptr));
+  REFUSED(aggf_trjdot_frames_t(p, p, 0, 7, 3, 5, d, 1, nullptr));  // float32 in, float64 out
+  REFUSED(aggf_trjdot_frames_outer(p, p, 1, 7, 0, 5, d, 1, nullptr));
+  REFUSED(aggf_trjdot_frames_outer(p, p, 0, 7, 3, 5, d, 1, nullptr));
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)2000, (int64_t)100000, (int64_t)1000000})
+    for (int32_t na : {1, 10, 257})
+      for (int32_t nb : {1, 33, 166, 4096}) {
+        const size_t wx = aggf_trjdot_cross_workspace_bytes(T, na, nb, 1);
+        for (int in = 0; in < 2; ++in)
+          for (int od = 0; od < 2; ++od) {
+            if (wx <= WS) RUNS(aggf_trjdot_cross(p, (char*)p + 4096, T, na, nb, in, d, od, od, ws, wx, nullptr));
+            if (in >= od) {
+              RUNS(aggf_trjdot_frames_t(p, (char*)p + 4096, in, T, na, nb, d, od, nullptr));
+              RUNS(aggf_trjdot_frames_outer(p, (char*)p + 4096, in, T, na, nb, d, od, nullptr));
+            }
+          }
+      }
   free(raw);
   printf("%d calls, %d unexpected statuses\n", n_calls, n_bad);
   return n_bad ? 1 : 0;

@@ -10,6 +10,8 @@ from .tmap import (
     RATMap,
 )
 from .tools import lmap_augvariables, smear_map
+from .jaxtools import jaxify_linearmap
+from .jaxlinearmap import JLinearMap
 
 __all__ = [
     "LinearMap",
@@ -24,4 +26,6 @@ __all__ = [
     "RATMap",
     "lmap_augvariables",
     "smear_map",
+    "jaxify_linearmap",
+    "JLinearMap",
 ]

@@ -388,6 +388,36 @@ int aggf_trjdot_frames(const void* points, int p_dtype, const void* factor, int 
                        int32_t N, int32_t n_cg, const void* trans, void* out, int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K8  Backward contractions of map application (the autograd Functions of
+ * aggforce_amd/_autograd.py; no reference counterpart: JAX differentiates
+ * jaxutil.trjdot's einsum itself).  All sums are float64-combined in a fixed
+ * order without atomics: results are bit-identical run to run.
+ *
+ * aggf_trjdot_cross  (K8a, the map gradient dL/dM of a 2-D factor):
+ *     out[i,j] (+)= sum_{t,d} A[t,i,d] * B[t,j,d]
+ *   A (T, n_a, 3) and B (T, n_b, 3) both in in_dtype; out (n_a, n_b) in out_dtype (any pair);
+ *   accumulate != 0 adds to out (chunked callers).  MFMA 16x16x4 tiles of 64 x 64, the frames
+ *   split into blocks whose float64 partial tiles go to ws; ws_bytes >= the query's value for the
+ *   same (T, n_a, n_b): both derive one plan from the shape alone.
+ * aggf_trjdot_frames_t  (K8b, transpose of K3c):
+ *     out[t,a,d] = sum_c F[t,c,a] * G[t,c,d]
+ *   G (T, n_cg, 3), F (T, n_cg, N), out (T, N, 3).
+ * aggf_trjdot_frames_outer  (K8c, the gradient of a per-frame factor):
+ *     out[t,c,a] = sum_d G[t,c,d] * P[t,a,d]
+ *   G (T, n_cg, 3), P (T, N, 3), out (T, n_cg, N).
+ *   K8b/K8c: both inputs in in_dtype; out_dtype may narrow float64 to float32 but not widen
+ *   (float32 inputs with a float64 out is AGGF_ERR_ARG: widen the inputs).  HBM-bound: the
+ *   (T, n_cg, N) array is read or written exactly once.
+ * ------------------------------------------------------------------------- */
+size_t aggf_trjdot_cross_workspace_bytes(int64_t T, int32_t n_a, int32_t n_b, int in_dtype);
+int aggf_trjdot_cross(const void* A, const void* B, int64_t T, int32_t n_a, int32_t n_b, int in_dtype,
+                      void* out, int out_dtype, int accumulate, void* ws, size_t ws_bytes, void* stream);
+int aggf_trjdot_frames_t(const void* G, const void* F, int in_dtype, int64_t T, int32_t n_cg, int32_t N,
+                         void* out, int out_dtype, void* stream);
+int aggf_trjdot_frames_outer(const void* G, const void* P, int in_dtype, int64_t T, int32_t n_cg,
+                             int32_t N, void* out, int out_dtype, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K4b/K4c  Dense-featuriser contractions of qp_feat_linear_map (any featuriser that
  * follows the reference's protocol: feats (T, N, n_feat), divs (T, n_feat, 3) per site).
  *
