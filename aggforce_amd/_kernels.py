@@ -152,7 +152,10 @@ def gram(
         out = torch.empty((n_red, n_red), dtype=torch.float64, device=dev)
         accumulate = False
     ind, cd = dtype_code(forces.dtype), dtype_code(compute_dtype)
-    need = l.aggf_gram_workspace_bytes(T, N, n_red, ind, cd, 1 if grp_ptr is not None else 0)
+    if first_col and grp_ptr is None:
+        need = l.aggf_gram_from_column_workspace_bytes(T, N, n_red, ind, cd, int(first_col))
+    else:
+        need = l.aggf_gram_workspace_bytes(T, N, n_red, ind, cd, 1 if grp_ptr is not None else 0)
     if ws_limit_bytes is not None:
         need = min(need, int(ws_limit_bytes))
     ws = workspace(need, dev, "gram")

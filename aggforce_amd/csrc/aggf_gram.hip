@@ -1521,12 +1521,31 @@ static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_p
 
 using namespace aggf;
 
-extern "C" size_t aggf_gram_workspace_bytes(int64_t T, int32_t N, int32_t n_red, int in_dtype,
-                                            int compute_dtype, int has_groups) {
+static size_t gram_workspace_query(int64_t T, int32_t N, int32_t n_red, int in_dtype, int compute_dtype, bool has_groups,
+                                   int32_t first_col) {
   if (T <= 0 || N <= 0 || n_red <= 0) return 0;
   GramPlan p;
-  make_plan(T, N, n_red, in_dtype, compute_dtype, has_groups != 0, true, 0, true, &p);
+  make_plan(T, N, n_red, in_dtype, compute_dtype, has_groups, true, 0, true, &p, first_col);
   return table_bytes(p) + (size_t)round_up((int64_t)p.slab_bytes, 256) + p.pack_bytes + 1024;
+}
+
+extern "C" size_t aggf_gram_workspace_bytes(int64_t T, int32_t N, int32_t n_red, int in_dtype,
+                                            int compute_dtype, int has_groups) {
+  return gram_workspace_query(T, N, n_red, in_dtype, compute_dtype, has_groups != 0, 0);
+}
+
+// first_col > 0 takes no straddling form: rows that are not whole 16-byte pieces with N % 128 != 0 leave the in-place
+// kernel for the pack + tile pipeline, whose pack chunk the query must plan -- sized by aggf_gram's query, which plans
+// in place, the chunks were carved out of a slab-only workspace (one pack, table, tile and reduce launch per few
+// thousand frames).  An in-place plan keeps aggf_gram's workspace and with it aggf_gram's split count: the tiles outside
+// the leading block stay bit-identical to aggf_gram's.
+extern "C" size_t aggf_gram_from_column_workspace_bytes(int64_t T, int32_t N, int32_t n_red, int in_dtype,
+                                                        int compute_dtype, int32_t first_col) {
+  if (first_col < 0 || first_col % TILE != 0) return 0;
+  if (T <= 0 || N <= 0 || n_red <= 0) return 0;
+  GramPlan p;
+  make_plan(T, N, n_red, in_dtype, compute_dtype, false, true, 0, true, &p, first_col);
+  return gram_workspace_query(T, N, n_red, in_dtype, compute_dtype, false, p.direct ? 0 : first_col);
 }
 
 static int gram_impl(const void* F, int64_t T, int32_t N, int in_dtype, int compute_dtype,

@@ -168,8 +168,10 @@ __global__ __launch_bounds__(256) void not_close_kernel(const T* __restrict__ a,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const double x = (double)a[i], y = (double)b[i];
-    // np.isclose: finite -> |x-y| <= atol + rtol|y|; equal infinities are close; NaN never
-    const bool ok = (x == y) || (fabs(x - y) <= atol + rtol * fabs(y));
+    // np.isclose (equal_nan=False): equal values (infinities of one sign included) are close; otherwise both must be
+    // finite with |x-y| <= atol + rtol|y| -- an infinity is close to nothing but itself (inf <= inf would say it is);
+    // NaN is close to nothing
+    const bool ok = (x == y) || (isfinite(x) && isfinite(y) && fabs(x - y) <= atol + rtol * fabs(y));
     bad |= !ok;
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);

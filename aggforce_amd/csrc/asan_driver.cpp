@@ -55,8 +55,10 @@ int main() {
   for (int64_t T : Ts)
     for (int32_t N : Ns) {
       for (int in = 0; in < 2; ++in)
-        for (int cd = 0; cd < 2; ++cd)
+        for (int cd = 0; cd < 2; ++cd) {
           for (int g = 0; g < 2; ++g) sink += aggf_gram_workspace_bytes(T, N, N > 3 ? N - N / 3 : N, in, cd, g);
+          for (int32_t fc : {0, 100, 128, 512}) sink += aggf_gram_from_column_workspace_bytes(T, N, N, in, cd, fc);
+        }
       sink += aggf_linearmap_apply_workspace_bytes(T, N, N / 16 + 1);
       sink += aggf_gram_pair_workspace_bytes(T, N, 128, AGGF_F64);
       sink += aggf_pair_dist_var_workspace_bytes(T, N);

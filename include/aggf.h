@@ -75,7 +75,7 @@ int aggf_device_info(int32_t* cu_count, size_t* free_bytes, size_t* total_bytes)
  * F needs the alignment of its element type only (a frame block may start at any row of
  * a larger array) and rows need not be multiples of 16 bytes (odd N); nothing is read
  * beyond F + T*3*N elements.  The launch plan -- and with it the workspace size -- depends
- * on (T, N, n_red, dtypes, has_groups) alone.
+ * on (T, N, n_red, dtypes, has_groups) alone (aggf_gram_from_column: and first_col).
  * G: (n_red, n_red) float64, full symmetric matrix; accumulate != 0 adds to it
  * (frame chunks, cross-validation folds).  Partial sums are combined in a fixed
  * order: two runs are bit-identical.
@@ -96,7 +96,14 @@ int aggf_gram(const void* F, int64_t T, int32_t N, int in_dtype, int compute_dty
  * either left untouched (in-place tile kernel: N % 128 == 0, in_dtype == compute_dtype or
  * float32 frames with float64 products) or overwritten with its own correct values (any other layout computes the
  * whole matrix), so the caller may paste its copy afterwards either way.  accumulate != 0 with
- * first_col > 0 is refused (AGGF_ERR_ARG): the two cases would differ there. */
+ * first_col > 0 is refused (AGGF_ERR_ARG): the two cases would differ there.  The plan depends on
+ * first_col too: size ws with aggf_gram_from_column_workspace_bytes (0 for a first_col that is
+ * not a non-negative multiple of 128).  Where the call reads F in place that is
+ * aggf_gram_workspace_bytes, so the tiles outside the leading block are bit-identical to
+ * aggf_gram's; where it does not (rows that are not whole 16-byte pieces, N % 128 != 0) it also
+ * plans the packed copy. */
+size_t aggf_gram_from_column_workspace_bytes(int64_t T, int32_t N, int32_t n_red, int in_dtype,
+                                             int compute_dtype, int32_t first_col);
 int aggf_gram_from_column(const void* F, int64_t T, int32_t N, int in_dtype, int compute_dtype,
                           int32_t n_red, int32_t first_col, double* G, int accumulate, void* ws,
                           size_t ws_bytes, void* stream);
@@ -215,8 +222,9 @@ int aggf_slice_gather(const void* P, int64_t T, int32_t N, int in_dtype, const i
 /* flag[0] = 1 if any element of x is NaN (map/core.py:13-16 _has_nans); flag must be
  * zeroed by the caller. */
 int aggf_has_nan(const void* x, int64_t count, int dtype, int32_t* flag, void* stream);
-/* flag[0] = 1 unless |a-b| <= atol + rtol*|b| everywhere (np.allclose, map/core.py:230-232);
- * flag must be zeroed by the caller. */
+/* flag[0] = 1 unless a and b are close everywhere as np.allclose (equal_nan=False) judges it
+ * (map/core.py:230-232): a == b, or both finite and |a-b| <= atol + rtol*|b|.  An infinity is
+ * close only to the same infinity; NaN is close to nothing.  flag must be zeroed by the caller. */
 int aggf_not_close(const void* a, const void* b, int64_t count, int dtype, double rtol,
                    double atol, int32_t* flag, void* stream);
 /* out[0] = sum of squares of x in float64, fixed summation order (agg.py:297).
