@@ -5,7 +5,8 @@
 // With P~ = P/s + A'A (same minimiser on the feasible set, positive definite whenever P
 // is positive definite on null(A)):
 //     L L' = P~,  Y = L^-1 A',  S = Y'Y = A P~^-1 A',  x = L^-T Y S^-1 b
-// followed by one refinement step on the constraint residual.  Everything is fp64 and
+// followed by refinement: n_refine steps on the constraint residual, then one on the full KKT residual (optimality
+// and constraints) with the same factors.  Everything is fp64 and
 // stays on the device: a blocked right-looking Cholesky (64-wide panels: LDS diagonal
 // factor + explicit 64x64 inverse, then MFMA GEMMs for the panel and the trailing
 // update) and triangular solves expressed as GEMMs with the inverted diagonal blocks.
@@ -991,7 +992,7 @@ struct SolveLayout {
   int npad, mpad, rpad;
   size_t e_Pt, e_Dinv, e_Ap, e_Y, e_Bw, e_S, e_DinvS, e_mr, e_nr;  // elements per problem
   size_t off_Pt, off_Dinv, off_Ap, off_Y, off_Bw, off_S, off_DinvS, off_Bp, off_T1, off_T2, off_Lam,
-      off_Z, off_Xt, off_X2, off_scal, total;
+      off_Z, off_Xt, off_X2, off_Pg, off_Mu, off_scal, total;
 };
 
 static SolveLayout solve_layout(int n, int m, int nrhs, int nprob) {
@@ -1029,6 +1030,8 @@ static SolveLayout solve_layout(int n, int m, int nrhs, int nprob) {
   l.off_Z = take(l.e_nr);
   l.off_Xt = take(l.e_nr);
   l.off_X2 = take(l.e_nr);
+  l.off_Pg = take(l.e_Pt);  // (G + l2 diag)/s again, for the optimality residual of the final refinement step
+  l.off_Mu = take(l.e_mr);  // the multipliers that go with Xt: P~ Xt = A' Mu
   l.off_scal = take(4);
   l.total = o;
   return l;
@@ -1058,9 +1061,8 @@ static int eq_qp_solve_impl(const double* G, int32_t n, double l2, const double*
             Y = M_(l.off_Y, mpad, l.e_Y), S = M_(l.off_S, mpad, l.e_S), DinvS = M_(l.off_DinvS, NB, l.e_DinvS),
             Bp = M_(l.off_Bp, rpad, l.e_mr), T1 = M_(l.off_T1, rpad, l.e_mr), T2 = M_(l.off_T2, rpad, l.e_mr),
             Lam = M_(l.off_Lam, rpad, l.e_mr), Z = M_(l.off_Z, rpad, l.e_nr), Xt = M_(l.off_Xt, rpad, l.e_nr),
-            X2 = M_(l.off_X2, rpad, l.e_nr);
+            X2 = M_(l.off_X2, rpad, l.e_nr), Pg = M_(l.off_Pg, npad, l.e_Pt), Mu = M_(l.off_Mu, rpad, l.e_mr);
   const Mat Bw_m = M_(l.off_Bw, mpad, l.e_Bw);  // (npad x mpad) view
-  const Mat Bw_r = M_(l.off_Bw, rpad, l.e_Bw);  // (mpad x rpad) view
   double* scal = reinterpret_cast<double*>(w + l.off_scal);  // 4 doubles per problem
   hipStream_t st = c.stream;
   const int np = nprob;
@@ -1113,24 +1115,45 @@ static int eq_qp_solve_impl(const double* G, int32_t n, double l2, const double*
   };
   y_times(Lam);
   solve_lower_t(c, Pt, npad, Dinv, Z, Xt, rpad);
-  // refinement on the constraint residual R = A Xt - B:  Xt -= P~^-1 A' S^-1 R
+  if (hipMemcpyAsync(Mu.p, Lam.p, (size_t)np * l.e_mr * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    c.rc = fail(AGGF_ERR_HIP, "%s: device copy failed", who);
+  // refinement on the constraint residual R = A Xt - B:  Xt -= P~^-1 A' S^-1 R,  Mu -= S^-1 R
   int64_t rb = ceil_div((int64_t)m * nrhs, 256 * 8);
   const unsigned resid_blocks = (unsigned)(rb < 1 ? 1 : rb > 64 ? 64 : rb);
-  for (int it = 0; it < n_refine; ++it) {
+  const int64_t n_mr = (int64_t)np * (int64_t)l.e_mr, n_nr = (int64_t)np * (int64_t)l.e_nr;
+  auto constraint_step = [&](double* resid_out) {
     gemm<false, false>(c, mpad, rpad, npad - (int)r0, 1.0, Ap.at(0, r0), Xt.at(r0, 0), 0.0, Lam);
-    if (it > 0) AGGF_LAUNCH(zero_scalar_kernel, dim3(np), dim3(1), 0, st, scal + 1, (int64_t)4);
+    if (resid_out != stats + 2) AGGF_LAUNCH(zero_scalar_kernel, dim3(np), dim3(1), 0, st, scal + 1, (int64_t)4);
     AGGF_LAUNCH(resid_kernel, dim3(resid_blocks, np), dim3(256), 0, st, Lam.p, Bp.p, m, nrhs, rpad, Lam.ps,
-                       it == 0 ? stats + 2 : scal + 1, (int64_t)4);
-    // padded rows/cols of A Xt - Bp are exact zeros, so the padded residual needs no masking.
-    // Bw's storage is reused as the (mpad x rpad) scratch for S^-1 R: per problem it holds at least
-    // mpad * rpad elements, but with its own per-problem stride
-    const Mat SR{Bw_r.p, rpad, Bw_r.ps};
-    schur_solve(Lam, SR);
-    y_times(SR);
+                       resid_out, (int64_t)4);
+    // padded rows/cols of A Xt - Bp are exact zeros, so the padded residual needs no masking.  S^-1 R replaces R
+    // (schur_solve reads its right-hand side into T1 first)
+    schur_solve(Lam, Lam);
+    AGGF_LAUNCH(axpy_kernel, flat_grid(n_mr), dim3(256), 0, st, Mu.p, Lam.p, -1.0, n_mr);
+    y_times(Lam);
     solve_lower_t(c, Pt, npad, Dinv, Z, X2, rpad);
-    AGGF_LAUNCH(axpy_kernel, flat_grid((int64_t)np * l.e_nr), dim3(256), 0, st, Xt.p, X2.p, -1.0,
-                       (int64_t)np * (int64_t)l.e_nr);
-  }
+    AGGF_LAUNCH(axpy_kernel, flat_grid(n_nr), dim3(256), 0, st, Xt.p, X2.p, -1.0, n_nr);
+  };
+  for (int it = 0; it < n_refine; ++it) constraint_step(it == 0 ? stats + 2 : scal + 1);
+  // One step on the FULL residual with the same factors.  The constraint steps leave the optimality residual
+  // r1 = A' Mu - P~ Xt at the level of the inverse-based triangular solves (forward errors of 25-60x those of a
+  // LAPACK solve at kappa 1e6-1e12, tests/test_gpu_solve_accuracy.py); the correction of [P~ -A'; A 0] is
+  //     Xt += P~^-1 r1,  then one constraint step on the new residual B - A Xt.
+  // r1 is formed as A'(Mu - A Xt) - Pg Xt with Pg = (G + l2 diag)/s: the optimality residual of the caller's problem
+  // itself, independent of the rounding of a caller-formed A'A.
+  AGGF_LAUNCH(build_pt_kernel, flat_grid((int64_t)npad * npad, np), dim3(256), 0, st, G, n, g_ps, npad, l2, l2_diag,
+                     scal, (int64_t)4, (const double*)nullptr, perm, Pg.p, Pg.ps);
+  AGGF_LAUNCH_OK();
+  gemm<false, false>(c, mpad, rpad, npad - (int)r0, 1.0, Ap.at(0, r0), Xt.at(r0, 0), 0.0, Lam);
+  if (hipMemcpyAsync(T1.p, Mu.p, (size_t)n_mr * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    c.rc = fail(AGGF_ERR_HIP, "%s: device copy failed", who);
+  AGGF_LAUNCH(axpy_kernel, flat_grid(n_mr), dim3(256), 0, st, T1.p, Lam.p, -1.0, n_mr);  // T1 = Mu - A Xt
+  gemm<true, false>(c, npad, rpad, mpad, 1.0, Ap, T1, 0.0, Z);                           // Z = A' T1
+  gemm<false, false>(c, npad, rpad, npad, -1.0, Pg, Xt, 1.0, Z);                        // Z -= Pg Xt
+  solve_lower(c, Pt, npad, Dinv, Z, X2, rpad);
+  solve_lower_t(c, Pt, npad, Dinv, X2, Z, rpad);
+  AGGF_LAUNCH(axpy_kernel, flat_grid(n_nr), dim3(256), 0, st, Xt.p, Z.p, 1.0, n_nr);
+  constraint_step(scal + 1);
   gemm<false, false>(c, mpad, rpad, npad - (int)r0, 1.0, Ap.at(0, r0), Xt.at(r0, 0), 0.0, Lam);
   AGGF_LAUNCH(resid_kernel, dim3(resid_blocks, np), dim3(256), 0, st, Lam.p, Bp.p, m, nrhs, rpad, Lam.ps, stats + 1,
                      (int64_t)4);
@@ -1145,8 +1168,9 @@ static int eq_qp_solve_impl(const double* G, int32_t n, double l2, const double*
 // reference): A x = e_i merely PINS m variables, x[pin[j]] = delta_ij.  With f the free variables,
 //     x_f = -P_ff^-1 P[f, pin[i]],
 // i.e. one Cholesky factorisation of the (n - m)^2 free block and one pair of triangular solves with m right-hand
-// sides -- no A'A product, no Schur complement, no refinement (the constraints hold exactly by construction):
-// about 90 of the general path's 330 dependent launches go, 2 ms of 7 at n = 4096, m = 256.
+// sides -- no A'A product, no Schur complement, no constraint refinement (the constraints hold exactly by
+// construction), then one refinement step on P_ff x_f + P[f, pin]: about 90 of the general path's 330 dependent
+// launches go, 2 ms of 7 at n = 4096, m = 256.
 
 // free[0..n-m) = the indices not in pin, ascending; bad[0] = 1 if a pin is out of range or repeated.  One workgroup.
 __global__ __launch_bounds__(256) void pinned_free_list_kernel(const int32_t* __restrict__ pin, int m, int n,
@@ -1354,7 +1378,7 @@ extern "C" int aggf_daxpby(int64_t n, double a, const double* x, double b, const
 // ---- one-hot constraint rows: m pinned variables (see pinned_* kernels) -------------------------------
 struct PinnedLayout {
   int npad, rpad;
-  size_t off_Pt, off_Dinv, off_Z, off_Xt, off_scal, off_idx, total;
+  size_t off_Pt, off_Dinv, off_Z, off_Xt, off_Pg, off_W, off_scal, off_idx, total;
 };
 static PinnedLayout pinned_layout(int n, int m) {
   PinnedLayout l;
@@ -1370,6 +1394,8 @@ static PinnedLayout pinned_layout(int n, int m) {
   l.off_Dinv = take(dinv_elems(l.npad) * 8);
   l.off_Z = take((size_t)l.npad * l.rpad * 8);
   l.off_Xt = take((size_t)l.npad * l.rpad * 8);
+  l.off_Pg = take((size_t)(l.npad + l.rpad) * l.npad * 8);  // the factorised matrix again, for the residual
+  l.off_W = take((size_t)l.npad * l.rpad * 8);
   l.off_scal = take(32);
   l.off_idx = take((size_t)n * 8);
   l.total = o;
@@ -1400,7 +1426,8 @@ extern "C" int aggf_eq_qp_solve_pinned(const double* G, int32_t n, double l2, co
   char* w = (char*)ws;
   const int npad = l.npad, rpad = l.rpad;
   const Mat Pt{reinterpret_cast<double*>(w + l.off_Pt), npad, 0}, Dinv{reinterpret_cast<double*>(w + l.off_Dinv), NB, 0},
-      Z{reinterpret_cast<double*>(w + l.off_Z), rpad, 0}, Xt{reinterpret_cast<double*>(w + l.off_Xt), rpad, 0};
+      Z{reinterpret_cast<double*>(w + l.off_Z), rpad, 0}, Xt{reinterpret_cast<double*>(w + l.off_Xt), rpad, 0},
+      Pg{reinterpret_cast<double*>(w + l.off_Pg), npad, 0}, Wm{reinterpret_cast<double*>(w + l.off_W), rpad, 0};
   double* scal = reinterpret_cast<double*>(w + l.off_scal);
   int32_t* free_idx = reinterpret_cast<int32_t*>(w + l.off_idx);
   int32_t* mark = free_idx + n;
@@ -1417,6 +1444,18 @@ extern "C" int aggf_eq_qp_solve_pinned(const double* G, int32_t n, double l2, co
                      (int64_t)0, 1, Z.p, npad, rpad, (int64_t)0);
   AGGF_LAUNCH_OK();
   solve_lower_t(c, Pt, npad, Dinv, Z, Xt, rpad);
+  // One refinement step on the residual of the system itself, R = B - P_ff Xt (B = -P[f, pin] / s), with the same
+  // factor: the inverse-based triangular solves leave forward errors of up to a few times LAPACK's at kappa >= 1e10
+  // (tests/test_gpu_solve_accuracy.py).  The matrix and B' are built again by the same kernel: bit-identical.
+  AGGF_LAUNCH(pinned_build_kernel, flat_grid((int64_t)(npad + rpad) * npad), dim3(256), 0, st, G, n, free_idx, nf,
+                     pin_idx, m, npad, rpad, l2, l2_diag, scal, Pg.p, stats);
+  AGGF_LAUNCH(pad_copy_kernel, flat_grid((int64_t)npad * rpad), dim3(256), 0, st, Pg.p + (int64_t)npad * npad, rpad, npad,
+                     (int64_t)0, 1, Z.p, npad, rpad, (int64_t)0);
+  AGGF_LAUNCH_OK();
+  gemm<false, false>(c, npad, rpad, npad, -1.0, Pg, Xt, 1.0, Z);  // Z = B - P_ff Xt
+  solve_lower(c, Pt, npad, Dinv, Z, Wm, rpad);
+  solve_lower_t(c, Pt, npad, Dinv, Wm, Z, rpad);
+  AGGF_LAUNCH(axpy_kernel, flat_grid((int64_t)npad * rpad), dim3(256), 0, st, Xt.p, Z.p, 1.0, (int64_t)npad * rpad);
   AGGF_LAUNCH_GATED(1024, pinned_scatter_kernel, flat_grid((int64_t)m * n), dim3(256), 0, st, Xt.p, rpad, free_idx, nf, pin_idx, m,
                      n, X, stats);
   AGGF_LAUNCH_OK();

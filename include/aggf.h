@@ -116,8 +116,9 @@ int aggf_gram_from_column(const void* F, int64_t T, int32_t N, int in_dtype, int
  *     x_i = argmin 1/2 x'(G + l2*diag(l2_diag)) x   s.t.  A x = B[:, i]
  * (what qpsolvers.solve_qp(P, q=0, A, b) is asked for).  One scaled, shifted
  * Cholesky factorisation P~ = P/s + A'A serves all right-hand sides; the Schur
- * complement A P~^-1 A' is factorised the same way; one refinement step on the
- * constraint residual follows.
+ * complement A P~^-1 A' is factorised the same way; n_refine refinement steps on the
+ * constraint residual follow, then one step on the full KKT residual (the optimality
+ * residual P x + A' lambda next to A x - b) with the same factors.
  * G: (n, n) float64 (not modified).  l2_diag: n float64 or NULL (= ones).
  * A: (m, n) float64.  B: (m, nrhs) float64 or NULL (= identity, nrhs must equal m).
  * X: (nrhs, n) float64, row i = x_i.
@@ -127,7 +128,7 @@ int aggf_gram_from_column(const void* F, int64_t T, int32_t N, int in_dtype, int
  * x -= P~^-1 A' S^-1 (A x - b) then remove the bias of that shift.
  * stats (device, 4 doubles): [0] 0 if ok, else 1-based index of the first
  * non-positive pivot (k for P~, n+k for the Schur complement); [1] max |A x - b|
- * after refinement; [2] max |A x - b| before refinement; [3] scale s.
+ * after refinement; [2] max |A x - b| before refinement (0 if n_refine == 0); [3] scale s.
  * ------------------------------------------------------------------------- */
 size_t aggf_eq_qp_workspace_bytes(int32_t n, int32_t m, int32_t nrhs);
 int aggf_eq_qp_solve(const double* G, int32_t n, double l2, const double* l2_diag,
@@ -167,7 +168,8 @@ int aggf_eq_qp_solve_batched_shift(const double* G, int32_t n, double l2, const 
  * identity -- the constraint rows of a slice coordinate map, `coord_map.standard_matrix @ con_mat` of
  * qplinear.py:82 for every configuration of the reference's tests: the constraints pin m variables,
  * x_i[pin_idx[j]] = delta_ij, and the rest follows from ONE factorisation of the free block,
- * x_f = -P_ff^-1 P[f, pin_idx[i]] -- no A'A product, no Schur complement, no refinement.
+ * x_f = -P_ff^-1 P[f, pin_idx[i]] -- no A'A product, no Schur complement, no constraint refinement; one
+ * refinement step on P_ff x_f + P[f, pin_idx[i]] with the same factor.
  * pin_idx: m int32 (device).  X: (m, n).  stats as above ([1] = [2] = 0: the constraints hold exactly;
  * [0] = -1 if pin_idx holds an index twice or outside 0..n-1: then no element of G or X is addressed through a pin
  * and X comes back as zeros). */
