@@ -18,8 +18,15 @@ probed once with unit displacements (and refused with ``ValueError`` if it is no
 
 Random numbers: JAX's threefry stream cannot be reproduced without JAX, so parity of the
 noised path is defined conditional on the noise: tests inject ``eps``; production draws
-from Philox4x32-10 keyed by (seed, global frame index, site, dim) on the device, which is
-independent of how frames are sharded over GPUs.
+on the device from Philox4x32-10 + Box-Muller (include/aggf.h, aggf_condnormal_augment).
+Element ``(t, site, dim)`` of a draw is element ``g = (frame_offset + t) * 3 n + 3 site + dim``
+of one flat stream (Philox quad ``g >> 2``, lane ``g & 3``), which is independent of how frames
+are sharded over GPUs.  The scalar-covariance forms draw from stream word 1
+(aggf_condnormal_sites / aggf_condnormal_augment), the full-covariance form draws its ``eps``
+from stream word 0 (aggf_synth_normal).  Draw ``k`` (0, 1, ...) of one augmenter -- every
+``sample`` / ``augment_trajectory`` / ``noise_sites`` call counts, with injected noise too, and
+``astype`` carries the count over -- uses the seed ``(seed + k * 0x9E3779B97F4A7C15) mod 2^64``.
+tests/noise_ref.py restates this on the host and tests/test_gpu_noise_stream.py compares values.
 """
 from typing import Callable, Final, Optional, Tuple, TypeVar
 
@@ -174,7 +181,7 @@ class CondNormal(Augmenter):
             raise ValueError(f"dtype must be float32 or float64; got {self.dtype}.")
         self.frame_offset = int(frame_offset)
         self._n_gen: Optional[int] = None if self._cov_matrix is None else self._cov_matrix.shape[0] // self.n_dim
-        self._calls = 0       # every sample()/augment call uses a fresh Philox stream offset
+        self._calls = 0       # every sample()/augment call draws under a fresh per-call seed (_next_stream)
         self._noise_queue = []  # injected standard-normal noise (tests / reproducibility)
 
     # ---- the maps ----------------------------------------------------------------------

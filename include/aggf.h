@@ -247,10 +247,22 @@ int aggf_sumsq(const void* x, int64_t count, int dtype, double* out, void* ws, s
  * compressed form -- atom a contributes M[mt_idx[j], a] = mt_val[j] for j in
  * [mt_ptr[a], mt_ptr[a+1]) -- (mt_val in aug_dtype); mean = M x: (T, n_cg, 3) and
  * noise: (T, n_cg, 3) in aug_dtype (the augmenter's dtype, float32 by default in
- * the reference); noise == NULL draws eps from Philox4x32-10 keyed by
- * (seed, frame_offset + t, site, dim), independent of sharding.  Outputs are in
- * NumPy's promotion of the two dtypes.  `mean` comes from aggf_linearmap_apply /
- * aggf_slice_gather with out_dtype = aug_dtype.
+ * the reference); noise == NULL draws eps from the library's noise stream, which
+ * is independent of sharding.  The stream (one definition for every entry point):
+ *     element    g = (frame_offset + t) * 3 n_cg + 3 site + dim   (flat index in the
+ *                whole trajectory's (frames, sites, 3) noise array)
+ *     quad       q = g >> 2, lane g & 3: Philox4x32-10 with counter
+ *                (q lo, q hi, stream lo, stream hi) and key (seed lo, seed hi) gives
+ *                four words; words (0, 1) make lanes 0 and 1, words (2, 3) lanes 2, 3
+ *     normals    u = (word + 0.5) / 2^32; rad = sqrt(-2 ln u1); the angle is the
+ *                double 6.283185307179586 * u2; even lane rad cos, odd lane rad sin
+ *                (float64, then rounded to aug_dtype)
+ *     stream     word 1 for the generated sites (this call, aggf_condnormal_sites),
+ *                word 0 for aggf_synth_normal
+ * `seed` is per call: the Python layer passes (seed + k * 0x9E3779B97F4A7C15) mod 2^64
+ * for the k-th draw of one augmenter (trajectory/gausstraj.py).  Pinned value by value
+ * by tests/noise_ref.py.  Outputs are in NumPy's promotion of the two dtypes.  `mean`
+ * comes from aggf_linearmap_apply / aggf_slice_gather with out_dtype = aug_dtype.
  * ------------------------------------------------------------------------- */
 int aggf_condnormal_augment(const void* coords, const void* forces, int64_t T, int32_t N,
                             int traj_dtype, const int32_t* mt_ptr, const int32_t* mt_idx,
@@ -581,10 +593,14 @@ int aggf_dot(const void* a, int a_dtype, const void* b, int b_dtype, int64_t cou
 
 /* ---------------------------------------------------------------------------
  * Synthetic trajectories for benchmarks and full-size property tests (no
- * reference counterpart).  out[t,a,d] = mean + sigma * z(seed, frame_offset+t, a, d)
- * with z a counter-based standard normal (Philox4x32-10 + Box-Muller), so any
- * sharding of the frame axis reproduces the same data.  If lattice != 0 the mean
- * of atom a is its position on a cubic lattice with that spacing (coordinates).
+ * reference counterpart).  out[t,a,d] = mean + sigma * z[g] with
+ * g = (frame_offset + t) * 3 N + 3 a + d the flat index and z the counter-based
+ * standard normal stream described at aggf_condnormal_augment (Philox4x32-10 +
+ * Box-Muller; quad g >> 2, lane g & 3) under stream word 0, so any sharding of the
+ * frame axis reproduces the same data.  If lattice != 0 the mean of atom a also
+ * carries its position on a cubic lattice with that spacing (coordinates): lattice *
+ * (a % side, (a / side) % side, a / side^2), side the smallest integer with
+ * side^3 >= N.
  * ------------------------------------------------------------------------- */
 int aggf_synth_normal(void* out, int64_t T, int32_t N, int dtype, uint64_t seed,
                       int64_t frame_offset, double mean, double sigma, double lattice,

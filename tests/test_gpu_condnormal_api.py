@@ -14,6 +14,7 @@ from aggforce_amd.map import AugmentedTMap, lmap_augvariables  # noqa: E402
 from aggforce_amd.qp import qp_linear_map  # noqa: E402
 from aggforce_amd.trajectory import AugmentedTrajectory, Augmenter, JCondNormal  # noqa: E402
 from oracle import aggforce_oracle as orc  # noqa: E402
+import noise_ref as R  # noqa: E402
 
 KBT = 0.6955215
 
@@ -51,6 +52,9 @@ def test_reference_literal_call_through_augmented_trajectory():
     out = tmap(traj)  # fresh Philox noise: statistical check only
     dev = (np.asarray(out.coords) - orc.trjdot(coords, cmat.astype(np.float32))).ravel()
     assert abs(dev.mean()) < 0.02 and abs(dev.var() / var - 1) < 0.1
+    # ... and the values (tests/noise_ref.py): the augmenter's injected draw was its call 0, so the application is call 1
+    eps_ref = R.site_noise_ref(len(coords), cmat.shape[0], np.float32, R.call_seed(42100, 1))
+    assert rel(out.coords, orc.trjdot(coords, cmat.astype(np.float32)) + np.float32(np.sqrt(var)) * eps_ref) < 1e-6
     # the reference's attributes
     assert augmenter.premap == coord_map.flat_call and augmenter.cov.shape == (15, 15) and augmenter.dtype == np.float32
     assert np.allclose(np.diag(augmenter.cov), var)
@@ -143,6 +147,13 @@ def test_full_covariance_draws_have_that_covariance_and_do_not_depend_on_shardin
     y = JCondNormal(cov=cov, seed=9, dtype=np.float32).sample(coords).reshape(T, 6).astype(np.float64)
     emp = y.T @ y / T
     assert np.max(np.abs(emp - cov)) < 0.02 and np.max(np.abs(y.mean(0))) < 0.01
+    # ... and the values: y = eps L' with eps the float32 stream of synth_normal (stream word 0) under call 0's seed
+    # (tests/noise_ref.py).  A float32 dot product of six terms is within 6 x 2^-24 of sum |eps_k L_jk|; an eps that
+    # the device rounded to the neighbouring float32 (its float64 value within 16 x 2^-53 of the reference's) adds
+    # 2 x 2^-24 of its term.
+    eps_ref = R.synth_normal_ref(T, n, np.float32, R.call_seed(9, 0)).reshape(T, 6).astype(np.float64)
+    L = np.linalg.cholesky(cov).astype(np.float32).astype(np.float64)
+    assert np.all(np.abs(y - eps_ref @ L.T) <= 8 * 2.0 ** -24 * (np.abs(eps_ref) @ np.abs(L).T))
     h = T // 2
     lo = JCondNormal(cov=cov, seed=9, dtype=np.float32).sample(coords[:h])
     hi = JCondNormal(cov=cov, seed=9, dtype=np.float32, frame_offset=h).sample(coords[h:])
