@@ -1,4 +1,4 @@
-"""Differentiable map application: five ``torch.autograd.Function``s over the HIP contractions.
+"""Differentiable map application and pair distances: eight ``torch.autograd.Function``s over the HIP kernels.
 
 Each Function is one kernel launch; the backward of each calls only these same Functions, so the set is closed under
 differentiation (``gradgradcheck``, force-matching double backward).  Shapes: points (T, N, 3), a 2-D map (n_cg, N),
@@ -14,9 +14,29 @@ FramesT(G, F)   out[t,a,d] = sum_c F[t,c,a] G[t,c,d] (K8b)  dG = ApplyFrames(H, 
 Outer(G, P)     out[t,c,a] = sum_d G[t,c,d] P[t,a,d] (K8c)  dG = ApplyFrames(P, H), dP = FramesT(G, H)
 ==============  ==========================================  =================================================
 
+Pair distances (``jaxutil.distances``): sites X (T, n, 3) and C (T, m, 3) (C is X for the self-distance matrix),
+u[t,i,j] = X[t,j] - C[t,i], pair arrays (T, m, n).  No (T, m, n, 3) array is formed by any of them.
+
+==========================  ===============================================  ==========================================
+Function                    forward                                          backward (upstream H, or GA and GB)
+==========================  ===============================================  ==========================================
+PairDist(X, C, square)      D[t,i,j] = |u| or u.u                     (K9a)  (dX, dC) = PairPull(W, X, C), W = 2 H or
+                                                                             where(D > 0, H / D, 0)
+PairPull(W, X, C) -> A, B   A[t,j] = sum_i W_ij u_ij, B[t,i] = -sum_j (K9b)  dW = PairDot(GA, GB, X, C),
+                                                                             (dX, dC) = PairPull(W, GA, GB)
+PairDot(V, Y, X, C)         out[t,i,j] = (V[t,j] - Y[t,i]).u          (K9a)  (dV, dY) = PairPull(H, X, C),
+                                                                             (dX, dC) = PairPull(H, V, Y)
+==========================  ===============================================  ==========================================
+
+A zero distance has weight 0: torch's own first-order value at |0|, and what keeps every higher order finite (the
+diagonal of a self-distance matrix does not depend on X at all).  A first-order backward of a distance (grad mode off)
+hands H and D to K9b, which divides as it reads: no W array exists.  With grad mode on W is built by torch ops on the
+saved D, which is connected to the graph.  PairPull is linear in (X, C), so the squared form's W = 2 H is taken as
+PairPull(H, 2 X, 2 C): no (T, m, n) product.
+
 Forward outputs have NumPy's promoted dtype; every gradient is returned in its input's dtype (the K8 kernels narrow in
-their epilogue, K3 and K3c results are cast).  A gradient autograd does not ask for is not computed: a constant map
-never launches K8a.  All launches go to the current stream.
+their epilogue, K9b does the same, K3, K3c and K9a results are cast).  A gradient autograd does not ask for is not
+computed: a constant map never launches K8a, and K9b skips the sum whose pointer is null.  All launches go to the current stream.
 """
 from __future__ import annotations
 
@@ -148,3 +168,102 @@ class Outer(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dP = FramesT.apply(G, H, P.dtype)
         return dG, dP, None
+
+
+# ------------------------------------------------------------------ pair distances (K9)
+def _pair_dtype(*arrays) -> torch.dtype:
+    ct = arrays[0].dtype
+    for a in arrays[1:]:
+        ct = torch.promote_types(ct, a.dtype)
+    return ct
+
+
+def _pull_dtype(ct: torch.dtype, x: torch.Tensor, c: torch.Tensor, want_x: bool, want_c: bool) -> torch.dtype:
+    """The one output dtype of a K9b call whose A goes to x and whose B goes to c: theirs if the wanted ones agree."""
+    wanted = {t.dtype for t, w in ((x, want_x), (c, want_c)) if w}
+    return wanted.pop() if len(wanted) == 1 else ct
+
+
+def _zeros_if_none(g: Optional[torch.Tensor], like: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    return torch.zeros(like.shape, dtype=dtype, device=like.device) if g is None else g
+
+
+class PairDist(torch.autograd.Function):
+    """D[t,i,j] = |X[t,j] - C[t,i]| (``square``: squared) on K9a (``aggf_pair_dist``), in the promoted dtype."""
+
+    @staticmethod
+    def forward(ctx, X, C, square=False):
+        ct = _pair_dtype(X, C)
+        D = K.pair_dist(_widened(X, ct), _widened(C, ct), K.PAIR_SQDIST if square else K.PAIR_DIST)
+        ctx.square = bool(square)
+        ctx.save_for_backward(X, C, D)
+        return D
+
+    @staticmethod
+    def backward(ctx, H):
+        X, C, D = ctx.saved_tensors
+        want_x, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_x or want_c):
+            return None, None, None
+        if ctx.square:
+            dX, dC = PairPull.apply(H, 2 * X, 2 * C, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c))
+        elif torch.is_grad_enabled():
+            pos = D > 0
+            W = torch.where(pos, H / torch.where(pos, D, torch.ones_like(D)), torch.zeros_like(D))
+            dX, dC = PairPull.apply(W, X, C, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c))
+        else:
+            ct = _pair_dtype(H, D)
+            dX, dC = K.pair_pull(_widened(H, ct), _widened(X, ct), _widened(C, ct), dv=_widened(D, ct),
+                                 want_a=want_x, want_b=want_c, out_dtype=_pull_dtype(ct, X, C, want_x, want_c))
+        return _as(dX, X.dtype), _as(dC, C.dtype), None
+
+
+class PairPull(torch.autograd.Function):
+    """(A, B), A[t,j,:] = sum_i W[t,i,j] u[t,i,j] and B[t,i,:] = -sum_j W[t,i,j] u[t,i,j], on K9b
+    (``aggf_pair_pull``), in ``out_dtype`` (default: promoted).  ``want_a`` / ``want_b`` False: that output is None."""
+
+    @staticmethod
+    def forward(ctx, W, X, C, want_a=True, want_b=True, out_dtype=None):
+        ct = _pair_dtype(W, X, C) if out_dtype is None else torch.promote_types(_pair_dtype(W, X, C), out_dtype)
+        A, B = K.pair_pull(_widened(W, ct), _widened(X, ct), _widened(C, ct), want_a=want_a, want_b=want_b,
+                           out_dtype=out_dtype or ct)
+        ctx.save_for_backward(W, X, C)
+        return A, B
+
+    @staticmethod
+    def backward(ctx, GA, GB):
+        W, X, C = ctx.saved_tensors
+        dW = dX = dC = None
+        if GA is None and GB is None:
+            return None, None, None, None, None, None
+        ct = _pair_dtype(W, X, C, *(g for g in (GA, GB) if g is not None))
+        GA, GB = _zeros_if_none(GA, X, ct), _zeros_if_none(GB, C, ct)
+        if ctx.needs_input_grad[0]:
+            dW = _as(PairDot.apply(GA, GB, X, C), W.dtype)
+        want_x, want_c = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if want_x or want_c:
+            dX, dC = PairPull.apply(W, GA, GB, want_x, want_c, _pull_dtype(ct, X, C, want_x, want_c))
+        return dW, _as(dX, X.dtype), _as(dC, C.dtype), None, None, None
+
+
+class PairDot(torch.autograd.Function):
+    """out[t,i,j] = (V[t,j] - Y[t,i]) . (X[t,j] - C[t,i]) on K9a (``aggf_pair_dist``, DOT), in the promoted dtype."""
+
+    @staticmethod
+    def forward(ctx, V, Y, X, C):
+        ct = _pair_dtype(V, Y, X, C)
+        out = K.pair_dist(_widened(X, ct), _widened(C, ct), K.PAIR_DOT, _widened(V, ct), _widened(Y, ct))
+        ctx.save_for_backward(V, Y, X, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, H):
+        V, Y, X, C = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dV = dY = dX = dC = None
+        ct = _pair_dtype(H, V, Y, X, C)
+        if need[0] or need[1]:
+            dV, dY = PairPull.apply(H, X, C, need[0], need[1], _pull_dtype(ct, V, Y, need[0], need[1]))
+        if need[2] or need[3]:
+            dX, dC = PairPull.apply(H, V, Y, need[2], need[3], _pull_dtype(ct, X, C, need[2], need[3]))
+        return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype)

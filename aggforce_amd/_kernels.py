@@ -1150,3 +1150,67 @@ def trjdot_frames_outer(g: torch.Tensor, p: torch.Tensor, out_dtype: torch.dtype
         check(lib().aggf_trjdot_frames_outer(ptr(g), ptr(p), dtype_code(g.dtype), T, n_cg, N, ptr(out),
                                              dtype_code(out_dtype), stream_ptr()), "aggf_trjdot_frames_outer")
     return out
+
+
+# ------------------------------------------------------------------ K9 pair distances (aggforce_amd/_autograd.py)
+PAIR_DIST, PAIR_SQDIST, PAIR_DOT = 0, 1, 2
+
+
+def _pair_sites(name: str, x: torch.Tensor, c: torch.Tensor):
+    """(T, m, n) of X (T, n, 3) and C (T, m, 3), which must share a float dtype and be contiguous."""
+    if (x.dim() != 3 or c.dim() != 3 or x.shape[2] != 3 or c.shape[2] != 3 or x.shape[0] != c.shape[0]
+            or x.dtype != c.dtype or x.dtype not in (torch.float32, torch.float64)):
+        raise ValueError(f"{name}: operands {tuple(x.shape)} {x.dtype}, {tuple(c.shape)} {c.dtype}")
+    if not (x.is_contiguous() and c.is_contiguous()):
+        raise ValueError(f"{name}: operands must be contiguous")
+    return x.shape[0], c.shape[1], x.shape[1]
+
+
+def pair_dist(x: torch.Tensor, c: torch.Tensor, mode: int = PAIR_DIST, v: Optional[torch.Tensor] = None,
+              y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(T, m, n) in the operands' dtype over u[t,i,j] = x[t,j] - c[t,i] (aggf_pair_dist): |u| (PAIR_DIST), u.u
+    (PAIR_SQDIST) or (v[t,j] - y[t,i]).u (PAIR_DOT, v shaped as x and y as c).  All operands share a dtype."""
+    T, m, n = _pair_sites("pair_dist", x, c)
+    if mode not in (PAIR_DIST, PAIR_SQDIST, PAIR_DOT):
+        raise ValueError(f"pair_dist: mode {mode}")
+    if mode == PAIR_DOT:
+        if v is None or y is None or (T, m, n) != _pair_sites("pair_dist", v, y) or v.dtype != x.dtype:
+            raise ValueError("pair_dist: PAIR_DOT needs v shaped as x and y shaped as c, in their dtype")
+    else:
+        v = y = None
+    out = torch.empty((T, m, n), dtype=x.dtype, device=x.device)
+    if out.numel() == 0:
+        return out
+    with _timed("pair_dist"):
+        check(lib().aggf_pair_dist(ptr(x), ptr(c), ptr(v), ptr(y), T, m, n, dtype_code(x.dtype), mode, ptr(out),
+                                   stream_ptr()), "aggf_pair_dist")
+    return out
+
+
+def pair_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, dv: Optional[torch.Tensor] = None,
+              want_a: bool = True, want_b: bool = True, out_dtype: Optional[torch.dtype] = None):
+    """(A, B): A[t,j,:] = sum_i w_ij u_ij (T, n, 3) and B[t,i,:] = -sum_j w_ij u_ij (T, m, 3) over u[t,i,j] =
+    x[t,j] - c[t,i], with the weights w (T, m, n) or, given ``dv``, (dv > 0 ? w / dv : 0) (aggf_pair_pull: one pass
+    over w for both).  An output that is not wanted is None and costs nothing.  All operands share a dtype at least
+    as wide as out_dtype (default: theirs)."""
+    T, m, n = _pair_sites("pair_pull", x, c)
+    out_dtype = out_dtype or x.dtype
+    for name, arr in (("w", w), ("dv", dv)):
+        if arr is not None and (tuple(arr.shape) != (T, m, n) or arr.dtype != x.dtype or not arr.is_contiguous()):
+            raise ValueError(f"pair_pull: {name} {tuple(arr.shape)} {arr.dtype} for sites {tuple(x.shape)} "
+                             f"{tuple(c.shape)} {x.dtype} (contiguous arrays of one dtype)")
+    if x.dtype == torch.float32 and out_dtype == torch.float64:
+        raise ValueError("pair_pull: float32 operands with float64 outputs: widen the operands")
+    a = torch.empty((T, n, 3), dtype=out_dtype, device=x.device) if want_a else None
+    b = torch.empty((T, m, 3), dtype=out_dtype, device=x.device) if want_b else None
+    if T * m * n == 0:  # empty sums
+        return (a.zero_() if want_a else None), (b.zero_() if want_b else None)
+    if not (want_a or want_b):
+        return None, None
+    l = lib()
+    need = l.aggf_pair_pull_workspace_bytes(T, m, n, dtype_code(x.dtype)) if want_b else 0
+    ws = workspace(need, x.device, "pairdist") if need else None
+    with _timed("pair_pull"):
+        check(l.aggf_pair_pull(ptr(w), ptr(dv), ptr(x), ptr(c), T, m, n, dtype_code(x.dtype), ptr(a), ptr(b),
+                               dtype_code(out_dtype), ptr(ws), need, stream_ptr()), "aggf_pair_pull")
+    return a, b

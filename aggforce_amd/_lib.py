@@ -72,6 +72,9 @@ PROTOTYPES = {
     "aggf_trjdot_cross": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, C.c_int, C.c_int, _vp, _sz, _vp]),
     "aggf_trjdot_frames_t": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _vp, C.c_int, _vp]),
     "aggf_trjdot_frames_outer": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _vp, C.c_int, _vp]),
+    "aggf_pair_dist": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, C.c_int, C.c_int, _vp, _vp]),
+    "aggf_pair_pull_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
+    "aggf_pair_pull": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _vp, C.c_int, _vp, _sz, _vp]),
     "aggf_feat_contract": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _dbl, _i64, _i32, _i32, _i32, _vp, C.c_int, _vp]),
     "aggf_feat_constraint_rows": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "aggf_gb_constraint_rows": (C.c_int, [_vp, _vp, C.c_int, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -280,6 +280,46 @@ int main() {
             }
           }
       }
+  // K9: the workspace query over the grid of shapes (overflowing ones included), refusals, empty shapes (no launch,
+  // no pointer needed), and plausible calls in every mode / dtype pair / output selection with the queried workspace
+  for (int64_t T : Ts)
+    for (int32_t N : Ns) sink += aggf_pair_pull_workspace_bytes(T, N / 16 + 1, N, 0) + aggf_pair_pull_workspace_bytes(T, N, N / 16 + 1, 1);
+  sink += aggf_pair_pull_workspace_bytes(INT64_MAX, 20000, 20000, 1) + aggf_pair_pull_workspace_bytes(-1, 5, 300, 0);
+  REFUSED(aggf_pair_dist(nullptr, p, nullptr, nullptr, 7, 3, 5, 1, AGGF_PAIR_DIST, d, nullptr));
+  REFUSED(aggf_pair_dist(p, p, nullptr, nullptr, 7, 3, 5, 1, AGGF_PAIR_DIST, nullptr, nullptr));
+  REFUSED(aggf_pair_dist(p, p, p, nullptr, 7, 3, 5, 1, AGGF_PAIR_DOT, d, nullptr));      // DOT without Y
+  REFUSED(aggf_pair_dist(p, p, nullptr, nullptr, 7, 3, 5, 2, AGGF_PAIR_DIST, d, nullptr));  // dtype
+  REFUSED(aggf_pair_dist(p, p, nullptr, nullptr, 7, 3, 5, 1, 3, d, nullptr));             // mode
+  REFUSED(aggf_pair_dist(p, p, nullptr, nullptr, -1, 3, 5, 1, AGGF_PAIR_DIST, d, nullptr));
+  REFUSED(aggf_pair_dist(p, p, nullptr, nullptr, (int64_t)1 << 40, 20000, 20000, 1, AGGF_PAIR_DIST, d, nullptr));  // T m n
+  RUNS(aggf_pair_dist(nullptr, nullptr, nullptr, nullptr, 0, 3, 5, 1, AGGF_PAIR_DIST, nullptr, nullptr));
+  RUNS(aggf_pair_dist(nullptr, nullptr, nullptr, nullptr, 7, 3, 0, 0, AGGF_PAIR_DOT, nullptr, nullptr));
+  REFUSED(aggf_pair_pull(nullptr, nullptr, p, p, 7, 3, 5, 1, d, d, 1, ws, WS, nullptr));
+  REFUSED(aggf_pair_pull(p, nullptr, p, nullptr, 7, 3, 5, 1, d, d, 1, ws, WS, nullptr));
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, 7, 3, 5, 0, d, d, 1, ws, WS, nullptr));        // float32 in, float64 out
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, 7, 3, 5, 1, d, d, 5, ws, WS, nullptr));
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, 7, -3, 5, 1, d, d, 1, ws, WS, nullptr));
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, 7, 3, 300, 1, d, d, 1, ws, 0, nullptr));       // two panels, no workspace
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, 7, 3, 300, 1, d, d, 1, nullptr, WS, nullptr));
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, 7, 3, 300, 1, d, d, 1, (char*)ws + 4, WS - 4, nullptr));  // misaligned partials
+  REFUSED(aggf_pair_pull(p, nullptr, p, p, INT64_MAX / 4, 1, 3, 1, d, d, 1, ws, WS, nullptr));
+  RUNS(aggf_pair_pull(nullptr, nullptr, nullptr, nullptr, 7, 0, 5, 1, nullptr, nullptr, 1, nullptr, 0, nullptr));
+  RUNS(aggf_pair_pull(p, nullptr, p, p, 7, 3, 5, 1, nullptr, nullptr, 1, nullptr, 0, nullptr));  // neither output
+  RUNS(aggf_pair_pull(p, nullptr, p, p, 7, 3, 300, 1, d, nullptr, 1, nullptr, 0, nullptr));      // A alone: no partials
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)100000})
+    for (int32_t m : {1, 17, 257, 8200})
+      for (int32_t n : {1, 65, 256, 257, 8200}) {
+        for (int in = 0; in < 2; ++in) {
+          const size_t wpl = aggf_pair_pull_workspace_bytes(T, m, n, in);
+          for (int mode : {AGGF_PAIR_DIST, AGGF_PAIR_SQDIST, AGGF_PAIR_DOT})
+            RUNS(aggf_pair_dist(p, (char*)p + 4096, p, (char*)p + 4096, T, m, n, in, mode, d, nullptr));
+          for (int od = 0; od <= in; ++od)
+            for (int sel = 1; sel < 4; ++sel)
+              if (wpl <= WS)
+                RUNS(aggf_pair_pull(p, sel == 3 ? p : nullptr, p, (char*)p + 4096, T, m, n, in, sel & 1 ? d : nullptr,
+                                    sel & 2 ? d + 4096 : nullptr, od, ws, wpl, nullptr));
+        }
+      }
   free(raw);
   printf("%d calls, %d unexpected statuses\n", n_calls, n_bad);
   return n_bad ? 1 : 0;

@@ -2,7 +2,11 @@
 
 The reference differentiates these through JAX; here the array type is the torch tensor and ``trjdot`` runs on the
 HIP kernels through the autograd Functions of ``_autograd`` (K3 / K3c forward, K8 backward), differentiable in both
-arguments to any order.  ``abatch`` and ``distances`` are plain torch code: autograd handles them.
+arguments to any order.  ``distances`` of GPU tensors runs on K9 through ``PairDist`` / ``PairPull`` / ``PairDot``:
+no (T, m, n, 3) displacement array is formed, forward or backward, and a zero distance (the diagonal of a self-distance
+matrix, coincident sites) has gradient 0 at every order -- plain torch returns NaN from the second order on.  Its
+other forms (``return_displacements``, CPU tensors, NumPy inputs, other dtypes) and ``abatch`` are plain torch code:
+autograd handles them.
 """
 from typing import Callable, Union
 
@@ -80,6 +84,19 @@ def abatch(
     return np.vstack(results)
 
 
+def _on_kernels(x, like=None) -> bool:
+    """A (T, n, 3) float32/float64 GPU tensor (with ``like``: on its device, with its number of frames)."""
+    ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.dim() == 3
+          and x.shape[2] == 3)
+    return ok and (like is None or (x.device == like.device and x.shape[0] == like.shape[0]))
+
+
+def _upper_triangles(dist: torch.Tensor) -> torch.Tensor:
+    n_sites = dist.shape[-1]
+    i0, i1 = torch.triu_indices(n_sites, n_sites, offset=1, device=dist.device)
+    return dist[:, i0, i1]
+
+
 def distances(
     xyz: torch.Tensor,
     cross_xyz: Union[torch.Tensor, None] = None,
@@ -94,6 +111,12 @@ def distances(
         raise ValueError("Cross distances only supported when return_matrix is truthy.")
     if return_displacements and not return_matrix:
         raise ValueError("Displacements only supported when return_matrix is truthy.")
+    if not return_displacements and _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
+        from ._autograd import PairDist
+
+        K.lib()
+        dist = PairDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, bool(square))
+        return dist if return_matrix else _upper_triangles(dist)
     xyz = xyz if isinstance(xyz, torch.Tensor) else torch.as_tensor(np.asarray(xyz))
     if cross_xyz is None:
         disp = xyz[:, None, :, :] - xyz[:, :, None, :]
@@ -106,8 +129,4 @@ def distances(
         dist = (disp**2).sum(dim=-1)
     else:
         dist = torch.linalg.vector_norm(disp, dim=-1)
-    if return_matrix:
-        return dist
-    n_sites = dist.shape[-1]
-    i0, i1 = torch.triu_indices(n_sites, n_sites, offset=1, device=dist.device)
-    return dist[:, i0, i1]
+    return dist if return_matrix else _upper_triangles(dist)

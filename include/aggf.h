@@ -440,6 +440,44 @@ int aggf_trjdot_frames_outer(const void* G, const void* P, int in_dtype, int64_t
                              int32_t N, void* out, int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K9  Differentiable pair distances (jaxutil.distances on GPU tensors and the autograd
+ * Functions PairDist / PairPull / PairDot of aggforce_amd/_autograd.py; reference
+ * jaxutil.py:103-187, which JAX differentiates itself).  X (T, n, 3), C (T, m, 3),
+ *     u[t,i,j] = X[t,j] - C[t,i]
+ * (C == X gives the self-distance matrix).  No (T, m, n, 3) array is formed.  All arrays of
+ * one call share `dtype` / `in_dtype` (widen mixed pairs first); base addresses need only
+ * element alignment; element offsets are 64-bit; any m, n >= 1.  An empty shape (T, m or n
+ * zero) returns AGGF_OK without a launch.
+ *
+ * aggf_pair_dist  (K9a): out (T, m, n) in `dtype`, by mode
+ *     AGGF_PAIR_DIST    out[t,i,j] = sqrt(u.u)   (dx^2 + dy^2 + dz^2 unscaled, in `dtype`: util.py:65-72)
+ *     AGGF_PAIR_SQDIST  out[t,i,j] = u.u
+ *     AGGF_PAIR_DOT     out[t,i,j] = (V[t,j] - Y[t,i]) . u[t,i,j],  V shaped as X, Y as C
+ *   V and Y are read in DOT mode only (NULL otherwise).  HBM-bound on the write: out is written
+ *   once, 3 (n + m) values are read per frame (6 (n + m) in DOT mode).
+ * aggf_pair_pull  (K9b): the two sums over a weight array W (T, m, n),
+ *     A[t,j,:] =  sum_i w[t,i,j] u[t,i,j]      (T, n, 3)
+ *     B[t,i,:] = -sum_j w[t,i,j] u[t,i,j]      (T, m, 3)
+ *   w = W if Dv == NULL, else w = (Dv > 0 ? W / Dv : 0) with Dv (T, m, n): the gradient of a
+ *   distance, zero where the distance is.  A or B may be NULL (an output nobody asked for costs
+ *   nothing; both NULL: nothing is launched).  Both in out_dtype, which may narrow float64 to
+ *   float32 but not widen.  HBM-bound on the read: W (and Dv) are read once for both outputs.
+ *   Sums run in a fixed order, beyond 16 terms in float64, without atomics: bit-identical run to
+ *   run.  Row sums over more than 1 KiB of a row of W (256 float32 or 128 float64 columns) go
+ *   through float64 partials in ws (only when B is asked for; the query returns 0 below that);
+ *   ws_bytes >= the query's value for the same shape and in_dtype.
+ * ------------------------------------------------------------------------- */
+#define AGGF_PAIR_DIST 0
+#define AGGF_PAIR_SQDIST 1
+#define AGGF_PAIR_DOT 2
+int aggf_pair_dist(const void* X, const void* C, const void* V, const void* Y, int64_t T, int32_t m,
+                   int32_t n, int dtype, int mode, void* out, void* stream);
+size_t aggf_pair_pull_workspace_bytes(int64_t T, int32_t m, int32_t n, int in_dtype);
+int aggf_pair_pull(const void* W, const void* Dv, const void* X, const void* C, int64_t T, int32_t m,
+                   int32_t n, int in_dtype, void* A, void* B, int out_dtype, void* ws, size_t ws_bytes,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------
  * K4b/K4c  Dense-featuriser contractions of qp_feat_linear_map (any featuriser that
  * follows the reference's protocol: feats (T, N, n_feat), divs (T, n_feat, 3) per site).
  *
