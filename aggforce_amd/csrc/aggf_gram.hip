@@ -14,6 +14,8 @@
 //                        full copy for (qp_form) is done by the LDS read pattern;
 //   gram_reduce_kernel   fixed-order fp64 sum of the split-K slabs into G (both
 //                        triangles) -- no float atomics, bit-reproducible.
+// Large float64 systems read in place take gram_tile_dma_kernel_x2 instead of the tile kernel: two tiles that share a
+// panel per workgroup of 16 waves (see there).
 #include <stdlib.h>
 
 #include "aggf_common.h"
@@ -560,6 +562,288 @@ __global__ __launch_bounds__(256) void build_tile_table_kernel(int32_t nt1, int3
 }
 
 // ---------------------------------------------------------------------------
+// The macro-tile kernel (float64 frames read in place, whole panels, nt1 >= routing::macro_min_tiles): ONE workgroup of
+// 16 waves per CU computes TWO 128x128 tiles over one frame range.  Waves 0-7 own the first tile, waves 8-15 the second,
+// each half in the 2 x 4 layout of 64 x 32 wave tiles of gram_tile_dma_kernel (same accumulators, operand offsets and
+// MFMA groups).  The two tiles of a macro-tile share panels: two neighbours (ti, tj), (ti, tj + 1) of a tile row stage
+// the panels ti, tj, tj + 1 -- three where two single-tile workgroups stage four -- and the diagonal tiles that a row
+// with an odd tile count leaves over go two by two with one panel each (build_macro_table_kernel).  At 32 tile rows a
+// stage fetches 768 panels instead of 1056.  Slabs, split-K and the reducer are those of the single-tile kernel.
+//
+// A stage has 12 DMA pieces per distinct panel (KB = 4), dealt round-robin to the 16 waves: a wave has up to PPW of
+// them, so every counted vmcnt comes from wave-uniform tallies: n_iss pieces issued so far against the pieces of the
+// stages that must have landed.  Invariant: all pieces of stage s have landed when a wave leaves the barrier of stage
+// s - 1 (every wave waits for its own pieces of the stages <= it + 1 in front of the barrier of stage `it`).
+// Template (tools/gram_macro_probe.hip times the forms; the library compiles MacroShipped only):
+//   NBUF ring slots of KB frames; iteration `it` issues the pieces of stage it + AHEAD;
+//   BURST    all of a wave's pieces right behind the stage barrier, otherwise piece q beside MFMA group q PG / PPW (between
+//            the group's operand reads and its MFMAs; the barrier group's piece behind the barrier);
+//   STAGGER  waves 8-15 meet the stage barrier at their FIRST group instead of the last (apply_dma_kernel's MODE 2): the
+//            two wave pairs of a SIMD are never in their operand-read / barrier phase together.  They still read stage
+//            `it` behind the barrier of stage `it`, so a slot is free one barrier later than without the stagger.
+template <int NBUF_, int KB_, int AHEAD_, bool BURST_, bool STAGGER_, int PG_ = 3 * KB_ / 4>
+struct MacroForm {
+  static constexpr int NBUF = NBUF_, KB = KB_, AHEAD = AHEAD_, PG = PG_;
+  static constexpr bool BURST = BURST_, STAGGER = STAGGER_;
+};
+constexpr int MACRO_PANELS = 3;  // distinct panels of a macro-tile, at most
+// shipped: two slots of 8 frames, one piece beside each of the first five MFMA groups, the barrier in front of the sixth
+// (c3 Gram launch 702.1 against 743.8 ms single-tile in one process; four-frame rings 728-734, every form with the
+// stagger or with the pieces behind the barrier slower than the single-tile kernel: profiles/macro_tile_probe.jsonl)
+using MacroShipped = MacroForm<2, 8, 1, false, false, 5>;
+
+template <int NBUF, int KB, int AHEAD, bool BURST, bool STAGGER, int PG>
+__global__ __launch_bounds__(1024, 1) void gram_tile_dma_kernel_x2(
+    const double* __restrict__ X, int64_t n_rows, int64_t ld, int32_t nt1, int32_t n_macro, int32_t ksplit,
+    const int32_t* __restrict__ macro_table, int64_t frames_per_split, double* __restrict__ slabs) {
+  using M = Mfma<double>;
+  constexpr int NW = 16;
+  constexpr int GROUPS = 3 * KB / 4;
+  constexpr int PANEL_ELEMS = KB * ROW_STRIDE;
+  constexpr int BUF_ELEMS = MACRO_PANELS * PANEL_ELEMS;
+  constexpr int PPP = KB * 3;                                  // pieces per panel and stage
+  constexpr int PPW = (MACRO_PANELS * PPP + NW - 1) / NW;      // per wave, at most: 3 (KB = 4) / 5 (KB = 8)
+  constexpr int NTHREADS = 64 * NW;
+  constexpr int KKS = 4 * ROW_STRIDE;
+  static_assert(KB == 4 || KB == 8, "frames per stage");
+  static_assert(PG >= 1 && PG <= GROUPS, "groups that take a DMA piece");
+  // slot of stage it + AHEAD: its last reader has passed a barrier before the first piece is issued
+  static_assert(AHEAD >= 1 && AHEAD <= NBUF - 1 - ((STAGGER && !BURST) ? 1 : 0), "ring depth");
+  // a piece behind the barrier of stage `it` is waited for at the barrier of stage it + 1, which answers for stage it + 2
+  static_assert(AHEAD >= 2 || (!BURST && !STAGGER && PG < GROUPS), "pieces behind the barrier need AHEAD >= 2");
+
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  double* smem = reinterpret_cast<double*>(smem_raw);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = wave >> 3;
+  const int wm = (wave & 7) >> 2, wn = wave & 3;
+
+  // workgroup -> (split, macro-tile), XCD-aware as in gram_tile_dma_kernel: an XCD runs 32 of these workgroups at a
+  // time and gets 32 CONSECUTIVE entries of the (split, macro-tile) list -- the 64 tiles of one 8x8 super-block, 16 panels
+  const int b = blockIdx.x;
+  const int v = (((b >> 3) >> 5) * 8 + (b & 7)) * 32 + ((b >> 3) & 31);
+  if (v >= ksplit * n_macro) return;  // grid is padded to a multiple of 256
+  const int ks = v / n_macro;
+  const int ent = v - ks * n_macro;
+  const int tA = macro_table[2 * ent], tB = macro_table[2 * ent + 1];
+  const bool lone = tB < 0;  // the last leftover diagonal tile: waves 8-15 run along and store nothing
+  const int tiA = tA >> 16, tjA = tA & 0xffff;
+  const int tiB = lone ? tiA : tB >> 16, tjB = lone ? tjA : tB & 0xffff;
+  // the distinct panels, in order of appearance
+  int p0 = tiA, p1 = -1, p2 = -1, np = 1;
+  auto add_panel = [&](int c) {
+    if (c != p0 && c != p1 && c != p2) {
+      if (np == 1) p1 = c; else p2 = c;
+      ++np;
+    }
+  };
+  add_panel(tjA);
+  add_panel(tiB);
+  add_panel(tjB);
+  auto slot_of = [&](int c) { return c == p0 ? 0 : (c == p1 ? 1 : 2); };
+  const int ti = half ? tiB : tiA, tj = half ? tjB : tjA;
+  const int tile_lin = ti * nt1 - ti * (ti - 1) / 2 + (tj - ti);  // row-major upper-triangle index
+
+  const int64_t t_begin = (int64_t)ks * frames_per_split;
+  int64_t t_end = t_begin + frames_per_split;
+  if (t_end > n_rows) t_end = n_rows;
+  const int n_it = t_begin < t_end ? (int)((t_end - t_begin + KB - 1) / KB) : 0;
+  const int last_rows = n_it > 0 ? (int)(t_end - t_begin - (int64_t)(n_it - 1) * KB) : KB;  // rows of the last stage
+
+  // this wave's DMA pieces (all wave-uniform but the lane's 16 bytes): piece p = wave + 16 q of the stage's 12 np
+  int64_t g_off[PPW];
+  int l_off[PPW], p_row[PPW];
+  bool p_ok[PPW];
+  int n_act = 0, n_act_last = 0;  // pieces of a whole stage / of the last stage when that is ragged
+#pragma unroll
+  for (int q = 0; q < PPW; ++q) {
+    const int p = wave + NW * q;
+    const int panel = p / PPP;
+    const int unit = (p - panel * PPP) / 3;
+    const int cp = p % 3;
+    const int pcol = panel == 0 ? p0 : (panel == 1 ? p1 : p2);
+    p_ok[q] = panel < np;
+    p_row[q] = unit;
+    g_off[q] = (int64_t)unit * ld + (int64_t)pcol * ROW_ELEMS + cp * 128 + lane * 2;
+    l_off[q] = panel * PANEL_ELEMS + unit * ROW_STRIDE + cp * 128;
+    n_act += p_ok[q] ? 1 : 0;
+    n_act_last += (p_ok[q] && unit < last_rows) ? 1 : 0;
+  }
+
+  // stage order rotated against the other workgroups that share a panel (gram_tile_dma_kernel): the 4 macro-tiles of
+  // a super-block row and the 8 of a super-block column get 8 different rotations
+  const int skew = n_it > 16 ? ((tiA + (tjA >> 1)) & 7) : 0;
+  auto stage_of = [&](int seq) { const int s = seq + skew; return s >= n_it ? s - n_it : s; };
+  // sequence position of the one stage with fewer than KB rows, or -1
+  const bool ragged = n_it > 0 && last_rows != KB;
+  const int ragged_seq = ragged ? (n_it - 1 - skew + (n_it - 1 - skew < 0 ? n_it : 0)) : -1;
+  // pieces this wave has issued once the stages 0..seq of the sequence are out
+  auto issued_upto = [&](int seq) {
+    const int s = seq < n_it - 1 ? seq : n_it - 1;
+    return (s + 1) * n_act - ((ragged_seq >= 0 && s >= ragged_seq) ? n_act - n_act_last : 0);
+  };
+  int n_iss = 0;
+  auto prep_stage = [&](int seq) {
+    // rows past the end of this split's frame range read as zeros
+    if (seq == ragged_seq) {
+      double* lbase = smem + (seq % NBUF) * BUF_ELEMS;
+      const int nz = KB - last_rows;
+      for (int e = tid; e < MACRO_PANELS * nz * ROW_ELEMS; e += NTHREADS) {
+        const int panel = e / (nz * ROW_ELEMS);
+        const int rem = e - panel * nz * ROW_ELEMS;
+        const int r = last_rows + rem / ROW_ELEMS, c = rem % ROW_ELEMS;
+        lbase[panel * PANEL_ELEMS + r * ROW_STRIDE + c] = 0;
+      }
+    }
+  };
+  auto issue_piece = [&](int seq, int q) {
+    const int st = stage_of(seq);
+    const int64_t t0 = t_begin + (int64_t)st * KB;
+    // (32-bit row test: a 64-bit compare has no scalar form and would run on the vector pipe beside the MFMAs)
+    if (seq < n_it && p_ok[q] && p_row[q] < (st == n_it - 1 ? last_rows : KB)) {
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)(X + t0 * ld + g_off[q]),
+          (__attribute__((address_space(3))) void*)(smem + (seq % NBUF) * BUF_ELEMS + l_off[q]), 16, 0, 0);
+      ++n_iss;
+    }
+  };
+  // every piece of the stages <= seq has landed (this wave's); later ones may stay in flight
+  auto wait_landed = [&](int seq) {
+    wait_vmcnt_dyn<8>(n_iss - issued_upto(seq));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+
+  f64x4 acc[4][2];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n) acc[m][n] = acc_zero<double>();
+  const int offA = slot_of(ti) * PANEL_ELEMS + (lane >> 4) * ROW_STRIDE + 3 * (wm * 64 + (lane & 15));
+  const int offB = slot_of(tj) * PANEL_ELEMS + (lane >> 4) * ROW_STRIDE + 3 * (wn * 32 + (lane & 15));
+
+#pragma unroll
+  for (int s = 0; s < AHEAD; ++s)
+    if (s < n_it) {
+      prep_stage(s);
+#pragma unroll
+      for (int q = 0; q < PPW; ++q) issue_piece(s, q);
+    }
+  wait_landed(0);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+
+  const int bar_g = (STAGGER && half) ? 0 : GROUPS - 1;  // the group whose MFMAs run behind the stage barrier
+  const bool prep_early = !BURST && bar_g != 0;          // the first piece goes out in front of the barrier
+  for (int it = 0; it < n_it; ++it) {
+    const bool issue_now = it + AHEAD < n_it;
+    if (issue_now && prep_early) prep_stage(it + AHEAD);
+    const double* pa = smem + (it % NBUF) * BUF_ELEMS;
+#pragma unroll
+    for (int kk = 0; kk < KB / 4; ++kk) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const int g = kk * 3 + d;
+        double a[4], bb[2];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) a[m] = pa[offA + kk * KKS + 48 * m + d];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) bb[n] = pa[offB + kk * KKS + 48 * n + d];
+        if (g == bar_g) {
+          // the operands of this group are in registers once the reads have returned: nobody needs the slot any more,
+          // and the group's MFMAs run while the waves meet
+          wait_landed(it + 1);
+          __builtin_amdgcn_s_barrier();
+          asm volatile("" ::: "memory");
+          if (issue_now) {
+            if (!prep_early) prep_stage(it + AHEAD);
+#pragma unroll
+            for (int q = 0; q < PPW; ++q)
+              if (BURST || q * PG / PPW == g) issue_piece(it + AHEAD, q);
+          }
+        } else if (!BURST && issue_now) {
+          // between the operand reads and the MFMAs of the group, as in gram_tile_dma_kernel
+#pragma unroll
+          for (int q = 0; q < PPW; ++q)
+            if (q * PG / PPW == g) issue_piece(it + AHEAD, q);
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int n = 0; n < 2; ++n) acc[m][n] = M::mma(a[m], bb[n], acc[m][n]);
+      }
+    }
+  }
+
+  if (half && lone) return;
+  double* slab = slabs + ((int64_t)tile_lin * ksplit + ks) * (TILE * TILE);
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = wm * 64 + m * 16 + M::row(lane, r);
+        const int col = wn * 32 + n * 16 + (lane & 15);
+        slab[row * TILE + col] = acc[m][n][r];
+      }
+}
+
+// Macro-tile table: entry k = two int32, the tiles (ti << 16) | tj of macro-tile k (the second -1: none).  First the
+// row pairs in the 8x8 super-block order of build_tile_table_kernel -- tile row ti is cut into pairs (ti, tj),
+// (ti, tj + 1) from its right end, i.e. a pair starts at every tj >= ti with nt1 - tj even -- then the diagonal tiles
+// (ti, ti) of the rows with an odd tile count, two by two in ascending order; an odd one of those stands alone.
+__host__ __device__ static inline int macro_leftovers(int nt1) { return (nt1 + 1) / 2; }
+__host__ __device__ static inline int macro_count(int nt1) {
+  const int n_left = macro_leftovers(nt1);
+  return (nt1 * (nt1 + 1) / 2 - n_left) / 2 + (n_left + 1) / 2;
+}
+__global__ __launch_bounds__(256) void build_macro_table_kernel(int32_t nt1, int32_t* __restrict__ table) {
+  __shared__ int wave_count[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t nsb = (nt1 + 7) / 8, n_super = nsb * (nsb + 1) / 2;
+  int64_t base = 0;
+  for (int64_t b0 = 0; b0 < n_super; b0 += 4) {
+    const int64_t sb = b0 + wave;
+    bool keep = false;
+    int ti = 0, tj = 0;
+    if (sb < n_super) {
+      const double w = 2.0 * (double)nsb + 1.0;
+      int64_t si = (int64_t)((w - sqrt(w * w - 8.0 * (double)sb)) * 0.5);
+      if (si < 0) si = 0;
+      if (si >= nsb) si = nsb - 1;
+      while (si > 0 && si * nsb - si * (si - 1) / 2 > sb) --si;
+      while (si + 1 < nsb && (si + 1) * nsb - (si + 1) * si / 2 <= sb) ++si;
+      const int64_t sj = si + (sb - (si * nsb - si * (si - 1) / 2));
+      ti = (int)si * 8 + (lane >> 3);
+      tj = (int)sj * 8 + (lane & 7);
+      keep = ti < nt1 && tj < nt1 && tj >= ti && ((nt1 - tj) & 1) == 0;
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wave_count[wave] = __popcll(mask);
+    __syncthreads();
+    int64_t off = base;
+    for (int w2 = 0; w2 < wave; ++w2) off += wave_count[w2];
+    if (keep) {
+      const int64_t k = off + __popcll(mask & ((1ull << lane) - 1ull));
+      table[2 * k] = (ti << 16) | tj;
+      table[2 * k + 1] = (ti << 16) | (tj + 1);
+    }
+    base += wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    __syncthreads();
+  }
+  // rows with an odd tile count: ti = (nt1 - 1) % 2, + 2, ...
+  const int n_left = macro_leftovers(nt1), first = (nt1 - 1) & 1;
+  for (int k = threadIdx.x; 2 * k < n_left; k += blockDim.x) {
+    const int a = first + 4 * k, c = a + 2;
+    table[2 * (base + k)] = (a << 16) | a;
+    table[2 * (base + k) + 1] = 2 * k + 1 < n_left ? ((c << 16) | c) : -1;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // G[(ti,tj) tile] (+)= sum_ks slab, and the mirrored tile.  grid = (n_tiles, 16): each
 // workgroup handles 8 rows of a tile... (16 row-groups of 8 rows x 128 cols, 256 threads,
 // 4 elements per thread).
@@ -1017,6 +1301,7 @@ struct GramPlan {
   int ksplit;
   bool edge = false;     // tile kernel reads rows that are not padded to whole panels (N % 128 != 0, in place)
   bool straddle = false; // ... and the rows are not whole 16-byte pieces: the last frame goes through gram_tail_row_kernel
+  bool macro = false;    // two tiles per workgroup of 16 waves (gram_tile_dma_kernel_x2); n_entries counts macro-tiles
   bool wide256 = false;  // small-system kernel: 113-128 columns on the 256-column panel (16 waves, 3 blocks per wave)
   int parts = 1;       // small-system kernel above 256 columns: workgroups that share a frame range and split the block list
   int64_t frames_per_split;
@@ -1024,9 +1309,12 @@ struct GramPlan {
   size_t slab_bytes, pack_bytes;
 };
 
-static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t max_splits, int stage_rows = 0) {
+static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t max_splits, int stage_rows = 0,
+                         int tiles_per_entry = 1) {
   // kb: 4 = float64 products, 8 = float32 (cost per frame and slab size); stage_rows: frames per LDS stage when that is
-  // not kb (float32 frames with float64 products: 8)
+  // not kb (float32 frames with float64 products: 8); tiles_per_entry: 2 = n_tiles counts macro-tiles (one workgroup
+  // of 16 waves per CU, `slots` = the CU count: a stage takes it what it takes a single-tile workgroup beside a second
+  // one, and it writes two slabs)
   if (stage_rows <= 0) stage_rows = kb;
   // Minimise a simple time model over the split count k: workgroups run in rounds of `slots`
   // (2 per CU); a workgroup costs its frames plus a fixed prologue/epilogue, and every
@@ -1046,7 +1334,7 @@ static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t
     const int64_t blocks = k * n_tiles;
     const double rounds = (double)ceil_div(blocks, slots);
     const double fpb = (double)round_up(ceil_div(frames, k), stage_rows);
-    const double cost = rounds * (fpb + fixed_frames) * us_per_frame + blocks * slab_us;
+    const double cost = rounds * (fpb + fixed_frames) * us_per_frame + blocks * tiles_per_entry * slab_us;
     if (cost < best_cost * (1.0 - 1e-6)) {
       best_cost = cost;
       best = k;
@@ -1108,9 +1396,11 @@ static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int comp
   // 19.6 against 13.2)
   // The thresholds are the constants of aggf_routing.h, generated from profiles/r05_routing.json (the measured crossovers;
   // tools/routing_sweep.py re-measures them).  AGGF_GRAM_ROUTE (measurement; read per call): "stream" = the streaming
-  // kernel wherever it can run, "tile" = never.
+  // kernel wherever it can run, "tile" = never, "single" = the single-tile kernel where the macro-tile kernel would
+  // run, "macro" = the macro-tile kernel below its threshold too.
   const char* route = getenv("AGGF_GRAM_ROUTE");
-  const bool force_stream = route && route[0] == 's', force_tile = route && route[0] == 't';
+  const bool force_stream = route && route[0] == 's' && route[1] == 't', force_tile = route && route[0] == 't';
+  const bool force_single = route && route[0] == 's' && route[1] == 'i', force_macro = route && route[0] == 'm';
   const bool f64p = compute_dtype == AGGF_F64;
   const int edge3_max = widen ? routing::stream_edge3_max_cols_widen : routing::stream_edge3_max_cols;
   const int edge4_max = widen ? routing::stream_edge4_max_cols_widen
@@ -1162,10 +1452,17 @@ static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int comp
     if (p->first_tile >= p->nt1) p->first_tile = p->nt1 - 1;  // always at least the last tile column
     p->n_entries = p->n_tiles - p->first_tile * (p->first_tile + 1) / 2;
   }
+  // Macro-tiles (gram_tile_dma_kernel_x2): float64 frames read in place in whole panels, from macro_min_tiles tile rows
+  // on (it won at every measured size from 8 tile rows up; up to 8 the parity tests pin the single-tile kernel's forms).
+  // Not aggf_gram_pair's two arrays, not a skipped leading block.
+  p->macro = p->direct && !p->edge && in_dtype == AGGF_F64 && compute_dtype == AGGF_F64 && first_col == 0 &&
+             !tiles_only && (p->nt1 >= routing::macro_min_tiles || force_macro) && !force_single;
+  if (p->macro) p->n_entries = macro_count(p->nt1);
+  const int tpe = p->macro ? 2 : 1;
   const int kb = compute_dtype == AGGF_F64 ? GramCfg<double>::KB : GramCfg<float>::KB;
-  const int stage_rows = p->direct && widen ? GramCfg<float>::KB : kb;
+  const int stage_rows = p->direct && widen ? GramCfg<float>::KB : (p->macro ? MacroShipped::KB : kb);
   const size_t cs = dtype_size(compute_dtype);
-  const int slots = 2 * device_cu_count();
+  const int slots = (p->macro ? 1 : 2) * device_cu_count();
   const size_t slab1 = (size_t)p->n_tiles * TILE * TILE * cs;  // one split
   const size_t row_bytes = (size_t)p->n_pad * 3 * cs;
   if (query) {
@@ -1183,7 +1480,7 @@ static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int comp
       if (cf > T) cf = T;
       p->chunk_frames = cf > 0 ? cf : 1;
     }
-    p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, 1 << 20, stage_rows);
+    p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, 1 << 20, stage_rows, tpe);
     p->slab_bytes = slab1 * p->ksplit;
     p->pack_bytes = p->direct ? 0 : round_up((int64_t)(p->chunk_frames * row_bytes), 256);
     return AGGF_OK;
@@ -1208,7 +1505,7 @@ static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int comp
   avail = avail > 512 ? avail - 512 : 0;  // room for the 256-byte roundings
   const int64_t max_splits = (int64_t)(avail / slab1);
   if (max_splits < 1) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small for one slab set");
-  p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, max_splits, stage_rows);
+  p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, max_splits, stage_rows, tpe);
   p->slab_bytes = slab1 * p->ksplit;
   return AGGF_OK;
 }
@@ -1226,10 +1523,44 @@ __global__ __launch_bounds__(256) void gram_tail_row_kernel(const TIn* __restric
   G[(int64_t)i * n_red + j] += s;
 }
 
+// table + macro-tile kernel + reducer; FORM: a MacroForm (the library: MacroShipped)
+template <typename FORM>
+static int launch_gram_macro(const double* X, int64_t rows, int64_t ld, const GramPlan& p, double* slabs,
+                             int32_t* tile_table, double* G, int32_t n_red, int accumulate, hipStream_t stream) {
+  constexpr int KB = FORM::KB;
+  const int ksplit = p.ksplit;
+  int64_t fps = round_up(ceil_div(rows, ksplit), KB);
+  if (fps < KB) fps = KB;
+  const int n_macro = macro_count(p.nt1);
+  const int64_t nblk = (int64_t)ksplit * n_macro;
+  if (round_up(nblk, 256) > 0x7fffffffLL) return fail(AGGF_ERR_ARG, "gram grid too large");
+  const size_t lds = (size_t)FORM::NBUF * MACRO_PANELS * KB * ROW_STRIDE * sizeof(double);
+  auto kernel = gram_tile_dma_kernel_x2<FORM::NBUF, KB, FORM::AHEAD, FORM::BURST, FORM::STAGGER, FORM::PG>;
+  static thread_local PerDeviceOnce attr_once;
+  bool& attr_done = *attr_once.flag();
+  if (!attr_done) {
+    AGGF_HIP_OK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_done = true;
+  }
+  AGGF_LAUNCH(build_macro_table_kernel, dim3(1), dim3(256), 0, stream, p.nt1, tile_table);
+  AGGF_LAUNCH_OK();
+  AGGF_LAUNCH((gram_tile_dma_kernel_x2<FORM::NBUF, KB, FORM::AHEAD, FORM::BURST, FORM::STAGGER, FORM::PG>),
+              dim3((unsigned)round_up(nblk, 256)), dim3(1024), lds, stream, X, rows, ld, p.nt1, n_macro, ksplit, tile_table,
+              fps, slabs);
+  AGGF_LAUNCH_OK();
+  AGGF_LAUNCH_GATED(1024, (gram_reduce_kernel<double>), dim3(p.n_tiles, TILE / 8), dim3(256), 0, stream,
+                     slabs, p.nt1, ksplit, n_red, accumulate, G, 0);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
 template <typename T, bool EDGE = false, typename TS = T>
 static int launch_gram(const TS* X, int64_t rows, int64_t ld, const GramPlan& p, T* slabs,
                        int32_t* tile_table, double* G, int32_t n_red, int accumulate, hipStream_t stream,
                        bool straddle = false) {
+  if constexpr (std::is_same<T, double>::value && std::is_same<TS, double>::value && !EDGE) {
+    if (p.macro) return launch_gram_macro<MacroShipped>(X, rows, ld, p, slabs, tile_table, G, n_red, accumulate, stream);
+  }
   constexpr int KB = GramCfg<TS>::KB;
   const int ksplit = p.ksplit;
   int64_t fps = round_up(ceil_div(rows, ksplit), KB);

@@ -1,5 +1,6 @@
 """GPU box: re-measure the crossovers behind profiles/r05_routing.json.  For every routing rule of aggf_gram's
-make_plan both routes are forced (AGGF_GRAM_ROUTE=stream | tile; AGGF_GRAM_PACK=serial | overlap for the pack rule) on
+make_plan both routes are forced (AGGF_GRAM_ROUTE=stream | tile, single | macro for the two tile kernels;
+AGGF_GRAM_PACK=serial | overlap for the pack rule) on
 systems around the threshold, ~6 GB of frames each; the table's `measurements` are replaced, the crossovers printed,
 and with --accept written into `thresholds` (then run tools/gen_routing.py and rebuild).
 
@@ -120,6 +121,32 @@ def main():
         del f
     if not only or "pack_overlap_min_pad" in only:
         proposed["pack_overlap_min_pad"] = over if over is not None else table["thresholds"]["pack_overlap_min_pad"]["value"]
+    # macro-tile kernel against the single-tile kernel by tile rows (float64 frames read in place in whole panels; "macro"
+    # forces the macro-tile kernel below its threshold too)
+    wins = []
+    for nt1 in (() if only and "macro_min_tiles" not in only else (8, 12, 16, 24, 32)):
+        f, gp, ga, N, T = system(128 * nt1, False, torch.float64)
+        row = {"rule": "macro_min_tiles", "tile_rows": nt1, "n_red": N, "atoms": N, "frames": T, "pairs": False, "dtypes": "float64->float64"}
+        for route in ("single", "macro"):
+            os.environ["AGGF_GRAM_ROUTE"] = route
+            _lib.load().aggf_coverage_reset()
+            row[route + "_ms"] = round(timed(lambda: K.gram(f, None, None, N, torch.float64)), 3)
+            row[route + "_kernel"] = sorted(p_.split("(")[0].replace("void aggf::", "") for p_, c in _lib.coverage(names=True).values()
+                                            if c > 0 and "gram_tile" in p_)
+        os.environ.pop("AGGF_GRAM_ROUTE", None)
+        wins.append((nt1, row["macro_ms"] < row["single_ms"]))
+        meas.append(row)
+        print(json.dumps(row), flush=True)
+        del f
+    if wins:
+        # from the smallest measured row count at and above which the macro-tile kernel always won; never below 9 (the
+        # single-tile forms up to 8 tile rows are pinned by parity tests); no win at all: a threshold nothing reaches
+        first = None
+        for nt1, won in reversed(wins):
+            if not won:
+                break
+            first = nt1
+        proposed["macro_min_tiles"] = max(9, first) if first is not None else 1 << 20
     table["measurements"] = meas
     table["proposed_by_last_sweep"] = {**table.get("proposed_by_last_sweep", {}), **proposed} if only else proposed
     for k, v in proposed.items():
