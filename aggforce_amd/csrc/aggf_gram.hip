@@ -1292,6 +1292,55 @@ __global__ __launch_bounds__(2 * WT > 1024 ? 1024 : 2 * WT) void gram_reduce_sma
 // ---------------------------------------------------------------------------
 enum GramStaging { STAGE_DMA8 = 3, STAGE_SMALL = 4 };  // 8-wave LDS-DMA tile kernel / single-tile streaming kernel
 
+// What a call computes, as far as its launch plan depends on it (no pointers: the kernels take F at any element-aligned
+// address, so the workspace query, which sees none, always describes the plan of the call).
+struct GramProblem {
+  int64_t T;
+  int32_t N, n_red;
+  int in_dtype, compute_dtype;
+  bool has_groups;
+  int32_t first_col = 0;    // aggf_gram_from_column: the caller keeps the leading first_col x first_col block of G
+  bool tiles_only = false;  // the caller's kernel is the tile kernel on arrays of whole panels (aggf_gram_pair)
+};
+
+// The AGGF_GRAM_* overrides (measurements and tests): everything the environment can change about a plan.  make_plan
+// reads them once per plan and keeps them in the plan.
+struct GramOverrides {
+  int ksplit;     // AGGF_GRAM_KSPLIT > 0: a fixed split count (tools/gram_ksplit_bench.py); read once per process
+  bool no_small;  // AGGF_GRAM_NO_SMALL: the tiled pipeline on small systems too (tests); read once per process
+  // the others are read on every call (tests switch them inside one process).  AGGF_GRAM_ROUTE: "stream" = the
+  // streaming kernel wherever it can run, "tile" = never, "single" = the single-tile kernel where the macro-tile kernel
+  // would run, "macro" = the macro-tile kernel below its threshold too
+  bool force_stream, force_tile, force_single, force_macro;
+  // AGGF_GRAM_PACK: "serial" = one pack buffer, one stream; "chunked" = the overlapped form's chunks on one stream
+  bool pack_serial, pack_one_stream;
+  // AGGF_GRAM_PACK_MIN_FRAMES (test hook): the smallest chunk of the overlapped pack pipeline, so that small inputs
+  // reach it; -1 = not set, below 8 = set, but the built-in minimum stays
+  int64_t pack_min_frames;
+};
+static GramOverrides read_overrides() {
+  static const char* const force_k = getenv("AGGF_GRAM_KSPLIT");
+  static const bool no_small = getenv("AGGF_GRAM_NO_SMALL") != nullptr;
+  const char *route = getenv("AGGF_GRAM_ROUTE"), *pack = getenv("AGGF_GRAM_PACK");
+  const char* min_frames = getenv("AGGF_GRAM_PACK_MIN_FRAMES");
+  return {force_k && atoi(force_k) > 0 ? atoi(force_k) : 0, no_small,
+          route && route[0] == 's' && route[1] == 't', route && route[0] == 't',
+          route && route[0] == 's' && route[1] == 'i', route && route[0] == 'm',
+          pack && pack[0] == 's', pack && pack[0] == 'c',
+          !min_frames ? -1 : (atoll(min_frames) > 0 ? atoll(min_frames) : 0)};
+}
+
+// The streaming kernel's class -- always one of the instantiations launch_small_class lists -- and the launch figures
+// that follow from it.
+struct SmallClass {
+  // gram_small_kernel's W, KBS, NV, NWV, C: panel width in reduced columns, 32 / 64 / 128 (8 waves, two workgroups per
+  // CU) or 256 / 512 (16 waves, one); frames per LDS stage; 16-byte loads per thread and stage, 3, 5 or 8; waves; 16 x 16
+  // blocks of the upper triangle per active wave
+  int width, kbs, nv, waves, blocks_per_wave;
+  int wt;  // slab edge = reducer width: 128 / 256 / 512
+  size_t raw_bytes, lds;
+};
+
 struct GramPlan {
   int32_t n_pad, nt1, n_tiles;
   int32_t first_tile = 0;  // tiles with tj < first_tile are skipped (aggf_gram_from_column; DMA8 direct path only)
@@ -1302,19 +1351,19 @@ struct GramPlan {
   bool edge = false;     // tile kernel reads rows that are not padded to whole panels (N % 128 != 0, in place)
   bool straddle = false; // ... and the rows are not whole 16-byte pieces: the last frame goes through gram_tail_row_kernel
   bool macro = false;    // two tiles per workgroup of 16 waves (gram_tile_dma_kernel_x2); n_entries counts macro-tiles
-  bool wide256 = false;  // small-system kernel: 113-128 columns on the 256-column panel (16 waves, 3 blocks per wave)
+  SmallClass small = {};  // STAGE_SMALL only
   int parts = 1;       // small-system kernel above 256 columns: workgroups that share a frame range and split the block list
-  int64_t frames_per_split;
   int64_t chunk_frames;  // frames per pack chunk (direct: T)
   size_t slab_bytes, pack_bytes;
+  GramOverrides env;
 };
 
-static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t max_splits, int stage_rows = 0,
+static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t max_splits, int forced, int stage_rows = 0,
                          int tiles_per_entry = 1) {
-  // kb: 4 = float64 products, 8 = float32 (cost per frame and slab size); stage_rows: frames per LDS stage when that is
-  // not kb (float32 frames with float64 products: 8); tiles_per_entry: 2 = n_tiles counts macro-tiles (one workgroup
-  // of 16 waves per CU, `slots` = the CU count: a stage takes it what it takes a single-tile workgroup beside a second
-  // one, and it writes two slabs)
+  // kb: 4 = float64 products, 8 = float32 (cost per frame and slab size); forced: GramOverrides::ksplit; stage_rows:
+  // frames per LDS stage when that is not kb (float32 frames with float64 products: 8); tiles_per_entry: 2 = n_tiles
+  // counts macro-tiles (one workgroup of 16 waves per CU, `slots` = the CU count: a stage takes it what it takes a
+  // single-tile workgroup beside a second one, and it writes two slabs)
   if (stage_rows <= 0) stage_rows = kb;
   // Minimise a simple time model over the split count k: workgroups run in rounds of `slots`
   // (2 per CU); a workgroup costs its frames plus a fixed prologue/epilogue, and every
@@ -1323,8 +1372,7 @@ static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t
   if (hi < 1) hi = 1;
   if (hi > max_splits) hi = max_splits;
   if (hi > 1024) hi = 1024;
-  static const char* force_k = getenv("AGGF_GRAM_KSPLIT");  // measurement: a fixed split count (tools/gram_ksplit_bench.py)
-  if (force_k && atoi(force_k) > 0) return (int)(atoi(force_k) < hi ? atoi(force_k) : hi);
+  if (forced > 0) return (int)(forced < hi ? forced : hi);
   const double us_per_frame = 0.64 * 4.0 / kb;     // one LDS stage = 48 MFMAs per wave, 2 waves per SIMD
   const double fixed_frames = 48.0;                // pipeline fill + slab store, in frame units
   const double slab_us = 2.0 * TILE * TILE * (kb == 4 ? 8 : 4) / 2.0e6;  // write + read at ~2 TB/s
@@ -1344,32 +1392,87 @@ static int choose_ksplit(int n_tiles, int64_t frames, int kb, int slots, int64_t
 }
 
 static size_t dtype_size(int dt) { return dt == AGGF_F64 ? 8 : 4; }
-static size_t table_bytes(const GramPlan& p) { return (size_t)round_up((int64_t)p.n_tiles * 8, 256); }
+
+// The workspace of a plan, [tile table | slabs | pack chunk]: byte offsets of the parts (each on a 256-byte boundary)
+// and what a call needs in all.  A QUERY answers total + 1024: make_plan, fitting a plan into given bytes, sets the
+// roundings' 512 bytes aside before it counts the slabs that fit, so the plan a query recommended fits what it asked for.
+struct GramWorkspace {
+  size_t slabs, pack, total;
+};
+static GramWorkspace workspace_layout(const GramPlan& p) {
+  const size_t slabs = (size_t)round_up((int64_t)p.n_tiles * 8, 256);
+  const size_t pack = slabs + (size_t)round_up((int64_t)p.slab_bytes, 256);
+  return {slabs, pack, pack + p.pack_bytes};
+}
+static size_t workspace_query_bytes(const GramPlan& p) { return workspace_layout(p).total + 1024; }
+
+// The class of the streaming kernel for a panel of `width` columns shared by `parts` workgroups per frame range; false:
+// no shipped instantiation can run it (the stage's raw frames do not fit the registers that carry them, or a workgroup
+// would have more blocks than accumulators).  Panel width 32 / 64 / 128 reduced columns with 32 / 16 / 8 frames per
+// stage (see gram_small_kernel).
+static bool small_class(const GramProblem& q, int width, int parts, SmallClass* c) {
+  const int64_t frame_bytes = (int64_t)3 * q.N * (int64_t)dtype_size(q.in_dtype);
+  auto pieces = [&](int frames) { return round_up(frames * frame_bytes, 16) / 16; };  // 16-byte pieces of a stage's raw frames
+  // the wider class when the stage's raw frames would not fit the registers (SM_MAXVEC 16-byte pieces per thread)
+  while (width < TILE && pieces(8 * TILE / width) > SM_MAXVEC * 512) width *= 2;
+  const bool f32p = q.compute_dtype == AGGF_F32;
+  const int nb16 = (q.n_red + 15) / 16, n_blocks = nb16 * (nb16 + 1) / 2;
+  c->width = width;
+  c->waves = width > TILE ? 16 : 8;
+  c->wt = width > TILE ? width : TILE;
+  c->kbs = width > 2 * TILE ? 4 : 8 * TILE / width;  // (the MFMA's K = 4 frames is the smallest stage)
+  // 256 columns: 8 frames per stage where they fit (one workgroup per CU: nothing covers a stage's barriers and group
+  // sums but its own MFMAs, and 4 frames are 15 MFMAs per wave)
+  // -- up to 5 blocks per wave (~200 columns): beyond, the longer MFMA phase spills (224 atoms 6.3 -> 9.2 ms)
+  if (width == 2 * TILE && pieces(8) <= 5 * 1024 && n_blocks <= 5 * 16) c->kbs = 8;
+  // (16-byte loads per thread and stage: at most SM_MAXVEC with 8 waves, 5 with 16)
+  const int64_t nv = ceil_div(pieces(c->kbs), 64 * c->waves);
+  if (nv > (c->waves == 16 ? 5 : SM_MAXVEC)) return false;
+  c->nv = nv <= 3 ? 3 : (nv <= 5 ? 5 : 8);
+  // blocks per active wave, within the shipped range of the panel: 32 columns 1 or 3 blocks in all, 64 columns 6 or 10,
+  // 128 columns 15 / 21 / 28 / 36, 256 columns 45 - 136 (8 frames: up to 80); 512 columns, a workgroup's share: 77 - 144
+  // with float64 products, 97 - 192 with float32
+  const int per_wave = (int)ceil_div(ceil_div((int64_t)n_blocks, parts), c->waves);
+  int lo = 1, hi = 1;
+  if (width == 64) hi = 2;
+  if (width == TILE) lo = 2, hi = 5;
+  if (width == 2 * TILE) lo = 3, hi = c->kbs == 8 ? 5 : 9;
+  if (width == 4 * TILE) lo = f32p ? 7 : 5, hi = f32p ? 12 : 9;
+  if (per_wave > hi) return false;
+  c->blocks_per_wave = per_wave < lo ? lo : per_wave;
+  c->raw_bytes = (size_t)pieces(c->kbs) * 16 + 16;  // small_raw_bytes<TIn>(N, kbs)
+  c->lds = (size_t)c->kbs * (3 * width + ROW_PAD) * dtype_size(q.compute_dtype) + c->raw_bytes +
+           (size_t)round_up(((int64_t)q.N + c->wt + 1) * 4, 16) + (size_t)3 * width * 4 * sizeof(unsigned short);
+  return true;
+}
 
 // One staging for both dtypes: LDS-DMA ring, 8 waves per tile, the stage's DMAs spread over the MFMA groups.
 // fp64 at C3: 757 ms (4 waves with the DMAs up front 786 ms, register staging 810 ms, pair tiles and the float32
 // "quad" shape no better: profiles/r04_pruned_variants.patch holds those kernels).
-static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int compute_dtype,
-                     bool has_groups, bool aligned, size_t ws_bytes, bool query, GramPlan* p, int32_t first_col = 0,
-                     bool tiles_only = false) {  // tiles_only: the caller's kernel is the tile kernel (aggf_gram_pair)
+// route_gram decides which kernel computes the problem and in which form: everything of the plan but its sizes.
+static void route_gram(const GramProblem& q, GramPlan* p) {
+  const int64_t T = q.T;
+  const int32_t N = q.N, n_red = q.n_red;
+  *p = GramPlan();
+  p->env = read_overrides();
+  const GramOverrides& env = p->env;
   p->n_pad = (int32_t)round_up(n_red, TILE);
   p->nt1 = p->n_pad / TILE;
   p->n_tiles = p->nt1 * (p->nt1 + 1) / 2;
-  // in place: no groups (`aligned`: the two-array form of aggf_gram_pair asks for 16-byte aligned arrays of whole
-  // panels; aggf_gram's kernels read F at any element-aligned address); N % 128 != 0 takes the EDGE form of the tile kernel
-  // (float32 frames with float64 products too: the tile kernel widens the operands as it reads them from LDS)
+  // in place: no groups; N % 128 != 0 takes the EDGE form of the tile kernel (float32 frames with float64 products
+  // too: the tile kernel widens the operands as it reads them from LDS).  The two-array form of aggf_gram_pair
+  // (tiles_only) asks for arrays of whole panels of one dtype.
   p->edge = N % TILE != 0;
-  const bool widen = in_dtype == AGGF_F32 && compute_dtype == AGGF_F64;
-  const bool rows16 = ((int64_t)3 * N * (int64_t)dtype_size(in_dtype)) % 16 == 0;
+  const bool widen = q.in_dtype == AGGF_F32 && q.compute_dtype == AGGF_F64;
+  const bool rows16 = ((int64_t)3 * N * (int64_t)dtype_size(q.in_dtype)) % 16 == 0;
   // rows that are not whole 16-byte pieces (an odd atom count; float32: N % 4 != 0): the piece across a row's end is
   // read into columns nobody uses, and the array's last row -- behind which nothing may be read -- is added by a
   // rank-3 update kernel.  Not for aggf_gram_from_column (the caller's leading block must stay what it is).
-  p->straddle = p->edge && !rows16 && !tiles_only && first_col == 0 && T >= 2;
-  p->direct = !has_groups && (in_dtype == compute_dtype || (widen && !tiles_only)) && aligned &&
-              (!p->edge || (!tiles_only && (rows16 || p->straddle)));
+  p->straddle = p->edge && !rows16 && !q.tiles_only && q.first_col == 0 && T >= 2;
+  p->direct = !q.has_groups && (q.in_dtype == q.compute_dtype || (widen && !q.tiles_only)) &&
+              (!p->edge || (!q.tiles_only && (rows16 || p->straddle)));
   if (!p->direct) p->straddle = false;
   p->staging = STAGE_DMA8;
-  static const char* no_small = getenv("AGGF_GRAM_NO_SMALL");  // tests: force the tiled pipeline on small systems
   // The streaming kernel (gram_small_kernel: the frames pass through LDS once, group sums / conversion / padding on the
   // way, only the 16 x 16 blocks of the upper triangle are multiplied) takes
   //   * n_red <= 128: 8 waves, two workgroups per CU, panel width 32 / 64 / 128 (6.5 ms at CLN025 x 4e6 frames when it
@@ -1387,89 +1490,96 @@ static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int comp
   //     tile kernel reads in place (N a multiple of 128, no groups, no conversion) keeps it from three tiles on (384
   //     atoms 11.4 against 15.2 ms), and from ~480 columns the pack + tile pipeline wins again with float64 products
   //     (500 atoms 19.6 against 27.9 ms).
-  const size_t raw_small = (size_t)round_up((int64_t)8 * 3 * N * (int64_t)dtype_size(in_dtype), 16);
-  const size_t raw_wide = (size_t)round_up((int64_t)4 * 3 * N * (int64_t)dtype_size(in_dtype), 16);  // 4 frames, 16 waves
-  const bool wide_fits = first_col == 0 && raw_wide <= (size_t)5 * 64 * 16 * 16;
   // (three tiles: the streaming kernel also beats the EDGE form of the tile kernel up to ~320 columns -- 260 atoms 9.1
   // against ~17 ms, 360 atoms 18.6 against 12.5; four tiles: the EDGE form wins
   // from ~400 columns with float64 products -- 448 atoms 16.5 against 24.5 ms -- and from ~480 with float32 -- 400 atoms
   // 19.6 against 13.2)
   // The thresholds are the constants of aggf_routing.h, generated from profiles/r05_routing.json (the measured crossovers;
-  // tools/routing_sweep.py re-measures them).  AGGF_GRAM_ROUTE (measurement; read per call): "stream" = the streaming
-  // kernel wherever it can run, "tile" = never, "single" = the single-tile kernel where the macro-tile kernel would
-  // run, "macro" = the macro-tile kernel below its threshold too.
-  const char* route = getenv("AGGF_GRAM_ROUTE");
-  const bool force_stream = route && route[0] == 's' && route[1] == 't', force_tile = route && route[0] == 't';
-  const bool force_single = route && route[0] == 's' && route[1] == 'i', force_macro = route && route[0] == 'm';
-  const bool f64p = compute_dtype == AGGF_F64;
+  // tools/routing_sweep.py re-measures them).
+  const bool f64p = q.compute_dtype == AGGF_F64;
   const int edge3_max = widen ? routing::stream_edge3_max_cols_widen : routing::stream_edge3_max_cols;
   const int edge4_max = widen ? routing::stream_edge4_max_cols_widen
                               : (f64p ? routing::stream_edge4_max_cols_f64 : routing::stream_edge4_max_cols_f32);
-  const bool wide = wide_fits && (p->nt1 == 2 || (force_stream && p->nt1 <= 4) ||
-                                  (p->nt1 == 3 && (!p->direct || (p->edge && n_red <= edge3_max))) ||
-                                  (p->nt1 == 4 && !p->direct && n_red <= (f64p ? routing::stream_pack4_max_cols_f64 : routing::stream_pack4_max_cols_f32)) ||
-                                  (p->nt1 == 4 && p->direct && p->edge && n_red <= edge4_max));
-  p->parts = 1;
-  p->wide256 = wide_fits && p->nt1 == 1 && n_red > routing::wide256_min_cols && !has_groups;
-  // (16-byte loads per thread and stage <= SM_MAXVEC; 3 N + xyz must fit the 16-bit member table)
-  if (((p->nt1 == 1 && raw_small <= (size_t)SM_MAXVEC * 64 * 8 * 16) || wide || p->wide256) && !no_small && !force_tile && !tiles_only && N < 21000 && aligned) {
-    // one output tile: the fused streaming kernel (group sums + conversion on the way into LDS, upper
-    // triangle blocks only); one slab per workgroup, 2 workgroups per CU over the frame axis
+  const bool wide = p->nt1 == 2 || (env.force_stream && p->nt1 >= 2 && p->nt1 <= 4) ||
+                    (p->nt1 == 3 && (!p->direct || (p->edge && n_red <= edge3_max))) ||
+                    (p->nt1 == 4 && !p->direct && n_red <= (f64p ? routing::stream_pack4_max_cols_f64 : routing::stream_pack4_max_cols_f32)) ||
+                    (p->nt1 == 4 && p->direct && p->edge && n_red <= edge4_max);
+  const bool wide256 = p->nt1 == 1 && n_red > routing::wide256_min_cols && !q.has_groups;
+  // A block's accumulators are 8 registers in float64 and 4 in float32: with float32 products a workgroup takes up
+  // to 192 blocks (12 per wave) -- 257-304 columns in ONE workgroup per frame range, up to 512 in three (a workgroup
+  // stages the whole panel whatever its share of the blocks).  12 GB of float32 frames, 144 / 192 / 224 / 288 blocks:
+  // 267 columns (400 atoms in bond pairs) 10.8 / 7.6 / 7.8 / 7.6 ms, 388 (villin's size) 13.9 / 10.8 / 10.8 / 10.8,
+  // 512 columns 15.1 / 12.5 / 12.4 / 47.6 -- beyond 13 blocks per wave the accumulators spill.
+  const int nb16 = (n_red + 15) / 16;
+  p->parts = p->nt1 > 2 ? (int)ceil_div((int64_t)nb16 * (nb16 + 1) / 2, f64p ? 144 : 192) : 1;
+  // the streaming kernel's panel (0: none): the 16-wave panels (256 columns: one or two tiles, 512: three or four) do
+  // not skip a leading block; one tile otherwise takes the 8-wave panels
+  int panel = 0;
+  if ((wide || wide256) && q.first_col == 0) panel = p->nt1 > 2 ? 4 * TILE : 2 * TILE;
+  else if (p->nt1 == 1) panel = n_red <= 32 ? 32 : (n_red <= 64 ? 64 : TILE);
+  // (3 N + xyz must fit the 16-bit member table)
+  if (panel && !env.no_small && !env.force_tile && !q.tiles_only && N < 21000 && small_class(q, panel, p->parts, &p->small)) {
     p->staging = STAGE_SMALL;
     p->n_entries = 1;
     p->direct = true;
-    p->chunk_frames = T;
-    p->pack_bytes = 0;
-    const int nb16 = (n_red + 15) / 16, n_blocks = nb16 * (nb16 + 1) / 2;
-    // A block's accumulators are 8 registers in float64 and 4 in float32: with float32 products a workgroup takes up
-    // to 192 blocks (12 per wave) -- 257-304 columns in ONE workgroup per frame range, up to 512 in three (a workgroup
-    // stages the whole panel whatever its share of the blocks).  12 GB of float32 frames, 144 / 192 / 224 / 288 blocks:
-    // 267 columns (400 atoms in bond pairs) 10.8 / 7.6 / 7.8 / 7.6 ms, 388 (villin's size) 13.9 / 10.8 / 10.8 / 10.8,
-    // 512 columns 15.1 / 12.5 / 12.4 / 47.6 -- beyond 13 blocks per wave the accumulators spill.
-    if (p->nt1 > 2) p->parts = (int)ceil_div((int64_t)n_blocks, compute_dtype == AGGF_F32 ? 192 : 144);
-    // one resident generation of workgroups (2 per CU; 1 with the 256- and 512-column panels), each looping over
-    // strided stages
-    int64_t nwg = (int64_t)(p->nt1 >= 2 || p->wide256 ? 1 : 2) * device_cu_count() / p->parts;
-    if (nwg < 1) nwg = 1;
-    const int64_t n_stage_all = ceil_div(T, 8);
-    if (nwg > n_stage_all) nwg = n_stage_all;
-    const int64_t edge = p->nt1 > 2 ? 4 * TILE : (p->wide256 ? 2 * TILE : p->n_pad);
-    const size_t slab1s = (size_t)p->parts * edge * edge * dtype_size(compute_dtype);
-    if (!query) {
-      if (ws_bytes < table_bytes(*p) + slab1s + 512) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small");
-      const int64_t max_splits = (int64_t)((ws_bytes - table_bytes(*p) - 512) / slab1s);
-      if (nwg > max_splits) nwg = max_splits;
-    }
-    p->frames_per_split = 0;
-    p->ksplit = (int)nwg;
-    p->slab_bytes = (size_t)p->ksplit * slab1s;
-    return AGGF_OK;
+    return;
   }
+  p->parts = 1;
   p->n_entries = p->n_tiles;
-  p->first_tile = 0;
-  if (first_col >= TILE && p->direct) {
-    p->first_tile = first_col / TILE;
+  if (q.first_col >= TILE && p->direct) {
+    p->first_tile = q.first_col / TILE;
     if (p->first_tile >= p->nt1) p->first_tile = p->nt1 - 1;  // always at least the last tile column
     p->n_entries = p->n_tiles - p->first_tile * (p->first_tile + 1) / 2;
   }
   // Macro-tiles (gram_tile_dma_kernel_x2): float64 frames read in place in whole panels, from macro_min_tiles tile rows
   // on (it won at every measured size from 8 tile rows up; up to 8 the parity tests pin the single-tile kernel's forms).
   // Not aggf_gram_pair's two arrays, not a skipped leading block.
-  p->macro = p->direct && !p->edge && in_dtype == AGGF_F64 && compute_dtype == AGGF_F64 && first_col == 0 &&
-             !tiles_only && (p->nt1 >= routing::macro_min_tiles || force_macro) && !force_single;
+  p->macro = p->direct && !p->edge && q.in_dtype == AGGF_F64 && f64p && q.first_col == 0 && !q.tiles_only &&
+             (p->nt1 >= routing::macro_min_tiles || env.force_macro) && !env.force_single;
   if (p->macro) p->n_entries = macro_count(p->nt1);
+}
+
+// The sizes of a streaming plan (ws_bytes == nullptr: as many slabs as the plan likes; otherwise those that fit): the
+// fused streaming kernel writes one slab per workgroup; one resident generation of workgroups (2 per CU; 1 with the
+// 256- and 512-column panels) shares the frame axis, each looping over strided stages.
+static int size_small(const GramProblem& q, const size_t* ws_bytes, GramPlan* p) {
+  p->chunk_frames = q.T;
+  p->pack_bytes = 0;
+  int64_t nwg = (int64_t)(p->small.waves == 16 ? 1 : 2) * device_cu_count() / p->parts;
+  if (nwg < 1) nwg = 1;
+  const int64_t n_stage_all = ceil_div(q.T, 8);
+  if (nwg > n_stage_all) nwg = n_stage_all;
+  const size_t slab1s = (size_t)p->parts * p->small.wt * p->small.wt * dtype_size(q.compute_dtype);
+  if (ws_bytes) {
+    const size_t table_bytes = workspace_layout(*p).slabs;
+    if (*ws_bytes < table_bytes + slab1s + 512) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small");
+    const int64_t max_splits = (int64_t)((*ws_bytes - table_bytes - 512) / slab1s);
+    if (nwg > max_splits) nwg = max_splits;
+  }
+  p->ksplit = (int)nwg;
+  p->slab_bytes = (size_t)p->ksplit * slab1s;
+  return AGGF_OK;
+}
+
+// The sizes of a tile-kernel plan: split count, slabs, pack chunk.
+static int size_tiles(const GramProblem& q, const size_t* ws_bytes, GramPlan* p) {
+  const int64_t T = q.T;
+  const bool f64p = q.compute_dtype == AGGF_F64, widen = q.in_dtype == AGGF_F32 && f64p;
+  const int forced = p->env.ksplit;
   const int tpe = p->macro ? 2 : 1;
-  const int kb = compute_dtype == AGGF_F64 ? GramCfg<double>::KB : GramCfg<float>::KB;
+  const int kb = f64p ? GramCfg<double>::KB : GramCfg<float>::KB;
   const int stage_rows = p->direct && widen ? GramCfg<float>::KB : (p->macro ? MacroShipped::KB : kb);
-  const size_t cs = dtype_size(compute_dtype);
+  const size_t cs = dtype_size(q.compute_dtype);
   const int slots = (p->macro ? 1 : 2) * device_cu_count();
   const size_t slab1 = (size_t)p->n_tiles * TILE * TILE * cs;  // one split
   const size_t row_bytes = (size_t)p->n_pad * 3 * cs;
-  if (query) {
+  p->pack_bytes = 0;
+  p->chunk_frames = T;
+  int64_t max_splits = 1 << 20;
+  if (!ws_bytes) {
     // recommended: slabs for the preferred split count + a pack chunk of up to 16 GiB (and at most a quarter of the
     // HBM that is free right now).  Round 2 capped the chunk at 1 GiB: 119 pack + table + tile + reduce launches at C3
     // with the pair constraints, 13 ms of slab sums and 2.5 ms of tile tables per step for nothing.
-    p->chunk_frames = T;
     if (!p->direct) {
       size_t free_b = 0, total_b = 0;
       size_t cap_b = (size_t)16 << 30;
@@ -1479,36 +1589,50 @@ static int make_plan(int64_t T, int32_t N, int32_t n_red, int in_dtype, int comp
       if (cf < 256) cf = 256;
       if (cf > T) cf = T;
       p->chunk_frames = cf > 0 ? cf : 1;
+      p->pack_bytes = (size_t)round_up((int64_t)(p->chunk_frames * row_bytes), 256);
     }
-    p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, 1 << 20, stage_rows, tpe);
-    p->slab_bytes = slab1 * p->ksplit;
-    p->pack_bytes = p->direct ? 0 : round_up((int64_t)(p->chunk_frames * row_bytes), 256);
-    return AGGF_OK;
+  } else {
+    // fit into the given workspace: the slabs of the split count the whole trajectory would like come first (at most
+    // half of the space), the pack chunk takes what is left
+    const size_t table_bytes = workspace_layout(*p).slabs;
+    if (*ws_bytes < table_bytes + 1024) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small");
+    const size_t room = *ws_bytes - table_bytes;
+    if (!p->direct) {
+      size_t slab_budget = slab1 * (size_t)choose_ksplit(p->n_entries, T, kb, slots, 1 << 20, forced) + 1024;
+      if (slab_budget > room / 2) slab_budget = room / 2;
+      const int64_t cf = (int64_t)((room - slab_budget) / row_bytes);
+      if (cf < 1) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small for one packed frame");
+      p->chunk_frames = cf < T ? cf : T;
+      p->pack_bytes = (size_t)round_up((int64_t)(p->chunk_frames * row_bytes), 256);
+    }
+    const size_t avail = room - p->pack_bytes;
+    max_splits = (int64_t)((avail > 512 ? avail - 512 : 0) / slab1);  // (512: room for the 256-byte roundings)
+    if (max_splits < 1) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small for one slab set");
   }
-  // fit into the given workspace: the slabs of the split count the whole trajectory would like come first (at most
-  // half of the space), the pack chunk takes what is left
-  p->pack_bytes = 0;
-  p->chunk_frames = T;
-  if (ws_bytes < table_bytes(*p) + 1024) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small");
-  ws_bytes -= table_bytes(*p);
-  size_t avail = ws_bytes;
-  if (!p->direct) {
-    size_t slab_budget = slab1 * (size_t)choose_ksplit(p->n_entries, T, kb, slots, 1 << 20) + 1024;
-    if (slab_budget > ws_bytes / 2) slab_budget = ws_bytes / 2;
-    int64_t cf = (int64_t)((ws_bytes - slab_budget) / row_bytes);
-    if (cf > T) cf = T;
-    if (cf < 1) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small for one packed frame");
-    p->chunk_frames = cf;
-    p->pack_bytes = (size_t)round_up((int64_t)(cf * row_bytes), 256);
-    avail = ws_bytes - p->pack_bytes;
-  }
-  avail = avail > 512 ? avail - 512 : 0;  // room for the 256-byte roundings
-  const int64_t max_splits = (int64_t)(avail / slab1);
-  if (max_splits < 1) return fail(AGGF_ERR_WORKSPACE, "gram workspace too small for one slab set");
-  p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, max_splits, stage_rows, tpe);
+  p->ksplit = choose_ksplit(p->n_entries, p->chunk_frames, kb, slots, max_splits, forced, stage_rows, tpe);
   p->slab_bytes = slab1 * p->ksplit;
   return AGGF_OK;
 }
+
+static int plan_gram(GramProblem q, const size_t* ws_bytes, GramPlan* p) {
+  route_gram(q, p);
+  // The recommended workspace of aggf_gram_from_column.  first_col > 0 takes no straddling form: rows that are not whole
+  // 16-byte pieces with N % 128 != 0 leave the in-place kernel for the pack + tile pipeline, whose pack chunk the query
+  // must plan -- sized by aggf_gram's query, which plans in place, the chunks were carved out of a slab-only workspace
+  // (one pack, table, tile and reduce launch per few thousand frames).  A plan that reads in place is sized as
+  // aggf_gram's: it keeps aggf_gram's workspace and with it aggf_gram's split count, so the tiles outside the leading
+  // block stay bit-identical to aggf_gram's.
+  if (!ws_bytes && q.first_col > 0 && p->direct) {
+    q.first_col = 0;
+    route_gram(q, p);
+  }
+  return p->staging == STAGE_SMALL ? size_small(q, ws_bytes, p) : size_tiles(q, ws_bytes, p);
+}
+
+// the plan with the workspace the library recommends (the workspace queries): cannot fail
+static void make_plan(const GramProblem& q, GramPlan* p) { (void)plan_gram(q, nullptr, p); }
+// the plan that fits a caller's workspace
+static int make_plan(const GramProblem& q, size_t ws_bytes, GramPlan* p) { return plan_gram(q, &ws_bytes, p); }
 
 // G += x x' over the three xyz components of ONE frame (float64 products whatever the dtypes of the call: exact
 // products of the stored values, the same in both triangles): the last frame of an array whose rows are not whole
@@ -1523,75 +1647,136 @@ __global__ __launch_bounds__(256) void gram_tail_row_kernel(const TIn* __restric
   G[(int64_t)i * n_red + j] += s;
 }
 
-// table + macro-tile kernel + reducer; FORM: a MacroForm (the library: MacroShipped)
-template <typename FORM>
-static int launch_gram_macro(const double* X, int64_t rows, int64_t ld, const GramPlan& p, double* slabs,
-                             int32_t* tile_table, double* G, int32_t n_red, int accumulate, hipStream_t stream) {
-  constexpr int KB = FORM::KB;
-  const int ksplit = p.ksplit;
-  int64_t fps = round_up(ceil_div(rows, ksplit), KB);
-  if (fps < KB) fps = KB;
-  const int n_macro = macro_count(p.nt1);
-  const int64_t nblk = (int64_t)ksplit * n_macro;
-  if (round_up(nblk, 256) > 0x7fffffffLL) return fail(AGGF_ERR_ARG, "gram grid too large");
-  const size_t lds = (size_t)FORM::NBUF * MACRO_PANELS * KB * ROW_STRIDE * sizeof(double);
-  auto kernel = gram_tile_dma_kernel_x2<FORM::NBUF, KB, FORM::AHEAD, FORM::BURST, FORM::STAGGER, FORM::PG>;
-  static thread_local PerDeviceOnce attr_once;
+// What differs between the tile kernels' launches besides the kernel: frames per LDS stage, block size, the multiple
+// the grid is rounded up to, dynamic LDS bytes.
+struct TileShape {
+  int kb, threads, grid_round;
+  size_t lds;
+};
+// gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, TWO, EDGE, TS>, the one shipped form of the single-tile kernel.
+// The stage barrier sits in front of the last MFMA group instead of behind it (its operands are in registers by then,
+// the 8 MFMAs run while the waves meet), and the DMA piece that goes with that group is issued BEHIND the barrier
+// (template ES = 1, ES_DMA_AFTER).  Same box, back to back: float32 c5 60.2 -> 58.6 ms, c2 3.25 -> 3.16 ms; float64
+// C3 756.4 -> 747.9 ms, c4 297.0 -> 293.9 ms.  With the piece in front of the barrier float64 is SLOWER than the
+// late barrier (757 -> 768 ms): the waves then meet right after the instruction that stalls longest.  Two groups
+// behind the barrier (ES = 2): c5 59.2 against 57.3 ms, C3 789 against 746 ms.
+template <typename TS>
+static constexpr TileShape single_tile_shape() {
+  return {GramCfg<TS>::KB, 512, 512, (size_t)3 * 2 * dma_panel_elems<TS>() * sizeof(TS)};
+}
+
+// Tile table + tile kernel + slab sum of one plan on `rows` frames at X, for every tile kernel (KERNEL: its
+// instantiation; T: the type of the slabs).  `tail`: the kernel's arguments behind `slabs`.
+template <auto KERNEL, typename T, typename TS, typename... Tail>
+static int launch_tiles(const TileShape& shape, const TS* X, int64_t rows, int64_t ld, const GramPlan& p, char* ws, double* G,
+                        int32_t n_red, int accumulate, hipStream_t stream, Tail... tail) {
+  int32_t* tile_table = reinterpret_cast<int32_t*>(ws);
+  T* slabs = reinterpret_cast<T*>(ws + workspace_layout(p).slabs);
+  int64_t fps = round_up(ceil_div(rows, p.ksplit), shape.kb);
+  if (fps < shape.kb) fps = shape.kb;
+  const int64_t grid = round_up((int64_t)p.ksplit * p.n_entries, shape.grid_round);  // n_entries = tiles actually computed
+  if (grid > 0x7fffffffLL) return fail(AGGF_ERR_ARG, "gram grid too large");
+  static thread_local PerDeviceOnce attr_once;  // (per instantiation, i.e. per kernel)
   bool& attr_done = *attr_once.flag();
   if (!attr_done) {
-    AGGF_HIP_OK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    AGGF_HIP_OK(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
     attr_done = true;
   }
-  AGGF_LAUNCH(build_macro_table_kernel, dim3(1), dim3(256), 0, stream, p.nt1, tile_table);
+  if (p.macro)
+    AGGF_LAUNCH(build_macro_table_kernel, dim3(1), dim3(256), 0, stream, p.nt1, tile_table);
+  else
+    AGGF_LAUNCH(build_tile_table_kernel, dim3(1), dim3(256), 0, stream, p.nt1, tile_table, p.first_tile);
   AGGF_LAUNCH_OK();
-  AGGF_LAUNCH((gram_tile_dma_kernel_x2<FORM::NBUF, KB, FORM::AHEAD, FORM::BURST, FORM::STAGGER, FORM::PG>),
-              dim3((unsigned)round_up(nblk, 256)), dim3(1024), lds, stream, X, rows, ld, p.nt1, n_macro, ksplit, tile_table,
-              fps, slabs);
+  AGGF_LAUNCH(KERNEL, dim3((unsigned)grid), dim3(shape.threads), shape.lds, stream, X, rows, ld, p.nt1, p.n_entries, p.ksplit,
+              tile_table, fps, slabs, tail...);
   AGGF_LAUNCH_OK();
-  AGGF_LAUNCH_GATED(1024, (gram_reduce_kernel<double>), dim3(p.n_tiles, TILE / 8), dim3(256), 0, stream,
-                     slabs, p.nt1, ksplit, n_red, accumulate, G, 0);
+  AGGF_LAUNCH_GATED(1024, (gram_reduce_kernel<T>), dim3(p.n_tiles, TILE / 8), dim3(256), 0, stream,
+                     slabs, p.nt1, p.ksplit, n_red, accumulate, G, p.first_tile);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
 }
 
+// the macro-tile kernel of a plan with `macro`; FORM: a MacroForm (the library: MacroShipped)
+template <typename FORM>
+static int launch_gram_macro(const double* X, int64_t rows, int64_t ld, const GramPlan& p, char* ws, double* G,
+                             int32_t n_red, int accumulate, hipStream_t stream) {
+  const TileShape shape = {FORM::KB, 1024, 256, (size_t)FORM::NBUF * MACRO_PANELS * FORM::KB * ROW_STRIDE * sizeof(double)};
+  return launch_tiles<gram_tile_dma_kernel_x2<FORM::NBUF, FORM::KB, FORM::AHEAD, FORM::BURST, FORM::STAGGER, FORM::PG>, double>(
+      shape, X, rows, ld, p, ws, G, n_red, accumulate, stream);
+}
+
+// the tile kernel the plan names on one array: macro-tile or single-tile (EDGE: rows not padded to whole panels)
 template <typename T, bool EDGE = false, typename TS = T>
-static int launch_gram(const TS* X, int64_t rows, int64_t ld, const GramPlan& p, T* slabs,
-                       int32_t* tile_table, double* G, int32_t n_red, int accumulate, hipStream_t stream,
-                       bool straddle = false) {
+static int launch_gram(const TS* X, int64_t rows, int64_t ld, const GramPlan& p, char* ws, double* G, int32_t n_red,
+                       int accumulate, hipStream_t stream) {
   if constexpr (std::is_same<T, double>::value && std::is_same<TS, double>::value && !EDGE) {
-    if (p.macro) return launch_gram_macro<MacroShipped>(X, rows, ld, p, slabs, tile_table, G, n_red, accumulate, stream);
+    if (p.macro) return launch_gram_macro<MacroShipped>(X, rows, ld, p, ws, G, n_red, accumulate, stream);
   }
-  constexpr int KB = GramCfg<TS>::KB;
-  const int ksplit = p.ksplit;
-  int64_t fps = round_up(ceil_div(rows, ksplit), KB);
-  if (fps < KB) fps = KB;
-  const int64_t nblocks = (int64_t)ksplit * p.n_tiles;
-  if (nblocks > 0x7fffffffLL) return fail(AGGF_ERR_ARG, "gram grid too large");
-  const size_t lds3 = (size_t)3 * 2 * dma_panel_elems<TS>() * sizeof(TS);
-  // The stage barrier sits in front of the last MFMA group instead of behind it (its operands are in registers by then,
-  // the 8 MFMAs run while the waves meet), and the DMA piece that goes with that group is issued BEHIND the barrier
-  // (template ES = 1, ES_DMA_AFTER).  Same box, back to back: float32 c5 60.2 -> 58.6 ms, c2 3.25 -> 3.16 ms; float64
-  // C3 756.4 -> 747.9 ms, c4 297.0 -> 293.9 ms.  With the piece in front of the barrier float64 is SLOWER than the
-  // late barrier (757 -> 768 ms): the waves then meet right after the instruction that stalls longest.  Two groups
-  // behind the barrier (ES = 2): c5 59.2 against 57.3 ms, C3 789 against 746 ms.
-  static thread_local PerDeviceOnce attr_once;
-  bool& attr_done = *attr_once.flag();
-  if (!attr_done) {
-    AGGF_HIP_OK(hipFuncSetAttribute((const void*)gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, false, EDGE, TS>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-    attr_done = true;
+  return launch_tiles<gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, false, EDGE, TS>, T>(
+      single_tile_shape<TS>(), X, rows, ld, p, ws, G, n_red, accumulate, stream, (const TS*)nullptr, (int64_t)0, (int32_t)0,
+      (int32_t)(EDGE ? ld : 0), (int32_t)(p.straddle ? 1 : 0));
+}
+
+// Streaming kernel + slab sum of the plan, if its class is this instantiation with C_LO <= C <= C_HI blocks per wave.
+template <typename TIn, typename TC, int NV, int KBS, int NWV, int W, int C_LO, int C_HI>
+static int launch_small(const GramPlan& p, const TIn* F, int64_t T, int32_t N, const int32_t* grp_ptr,
+                        const int32_t* grp_atoms, int32_t n_red, double* G, int accumulate, TC* slabs, hipStream_t stream) {
+  if (p.small.blocks_per_wave != C_LO) {
+    if constexpr (C_LO < C_HI)
+      return launch_small<TIn, TC, NV, KBS, NWV, W, C_LO + 1, C_HI>(p, F, T, N, grp_ptr, grp_atoms, n_red, G, accumulate, slabs,
+                                                                    stream);
+    else
+      return fail(AGGF_ERR_ARG, "aggf_gram: the plan names a streaming kernel the library does not contain");
   }
-  AGGF_LAUNCH(build_tile_table_kernel, dim3(1), dim3(256), 0, stream, p.nt1, tile_table, p.first_tile);
+  constexpr int WT = W > TILE ? W : TILE;
+  if (p.small.lds > 65536) {
+    static thread_local PerDeviceOnce attr_once;
+    bool& attr_done = *attr_once.flag();
+    if (!attr_done) {
+      AGGF_HIP_OK(hipFuncSetAttribute((const void*)gram_small_kernel<TIn, TC, NV, KBS, NWV, W, C_LO>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+      attr_done = true;
+    }
+  }
+  AGGF_LAUNCH((gram_small_kernel<TIn, TC, NV, KBS, NWV, W, C_LO>), dim3((unsigned)p.ksplit, (unsigned)p.parts), dim3(64 * NWV),
+              p.small.lds, stream, F, T, N, grp_ptr, grp_atoms, n_red, (int64_t)0 /* frames_per_split: ignored */,
+              (int32_t)p.small.raw_bytes, slabs);
   AGGF_LAUNCH_OK();
-  const int64_t nblk = (int64_t)ksplit * p.n_entries;  // n_entries = tiles actually computed
-  AGGF_LAUNCH((gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, false, EDGE, TS>), dim3((unsigned)round_up(nblk, 512)),
-                     dim3(512), lds3, stream, X, rows, ld, p.nt1, p.n_entries, ksplit, tile_table, fps, slabs,
-                     (const TS*)nullptr, (int64_t)0, 0, (int32_t)(EDGE ? ld : 0), (int32_t)(straddle ? 1 : 0));
-  AGGF_LAUNCH_OK();
-  AGGF_LAUNCH_GATED(1024, (gram_reduce_kernel<T>), dim3(p.n_tiles, TILE / 8), dim3(256), 0, stream,
-                     slabs, p.nt1, ksplit, n_red, accumulate, G, p.first_tile);
+  AGGF_LAUNCH_GATED(256, (gram_reduce_small_kernel<TC, WT>), dim3(WT), dim3(2 * WT > 1024 ? 1024 : 2 * WT), 0, stream, slabs,
+                     p.ksplit, n_red, accumulate, G, p.parts);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
+}
+
+// The shipped instantiations of the streaming kernel: register pieces NV (8 waves: 3, 5, 8; 16 waves: 3, 5) x (frames
+// per stage, waves, panel width) x blocks per wave C (first .. last).  small_class yields no other class.
+template <typename TIn, typename TC>
+static int launch_small_class(const GramPlan& p, const TIn* F, int64_t T, int32_t N, const int32_t* grp_ptr,
+                              const int32_t* grp_atoms, int32_t n_red, double* G, int accumulate, TC* slabs, hipStream_t stream) {
+  const SmallClass& c = p.small;
+#define AGGF_SMALL(NVC, KBC, NWC, WC, C_LO, C_HI)                            \
+  if (c.nv == NVC && c.kbs == KBC && c.waves == NWC && c.width == WC)        \
+    return launch_small<TIn, TC, NVC, KBC, NWC, WC, C_LO, C_HI>(p, F, T, N, grp_ptr, grp_atoms, n_red, G, accumulate, slabs, \
+                                                                stream)
+#define AGGF_SMALL_8(KBC, WC, C_LO, C_HI) \
+  AGGF_SMALL(3, KBC, 8, WC, C_LO, C_HI); AGGF_SMALL(5, KBC, 8, WC, C_LO, C_HI); AGGF_SMALL(8, KBC, 8, WC, C_LO, C_HI)
+#define AGGF_SMALL_16(KBC, WC, C_LO, C_HI) AGGF_SMALL(3, KBC, 16, WC, C_LO, C_HI); AGGF_SMALL(5, KBC, 16, WC, C_LO, C_HI)
+  AGGF_SMALL_8(32, 32, 1, 1);    // 1 or 3 blocks in all
+  AGGF_SMALL_8(16, 64, 1, 2);    // 6, 10
+  AGGF_SMALL_8(8, 128, 2, 5);    // 15, 21, 28, 36
+  AGGF_SMALL_16(8, 256, 3, 5);   // 256-column panel, 16 waves, 8 frames: up to 80 blocks
+  AGGF_SMALL_16(4, 256, 3, 9);   // 4 frames (the frames of 8 do not fit): 45, 55, 66, 78, 91, 105, 120, 136
+  // 512-column panel, a workgroup's share of the blocks: 77 - 144 with float64 products; with float32 a workgroup has
+  // at least 97, and up to 12 per wave, 192 in all
+  if constexpr (std::is_same<TC, double>::value) {
+    AGGF_SMALL_16(4, 512, 5, 9);
+  } else {
+    AGGF_SMALL_16(4, 512, 7, 12);
+  }
+#undef AGGF_SMALL_16
+#undef AGGF_SMALL_8
+#undef AGGF_SMALL
+  return fail(AGGF_ERR_ARG, "aggf_gram: the plan names a streaming kernel the library does not contain");
 }
 
 // side stream + events of the overlapped pack pipeline (gram_typed), created once per host thread and device
@@ -1620,143 +1805,24 @@ template <typename TIn, typename TC>
 static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_ptr,
                       const int32_t* grp_atoms, int32_t n_red, double* G, int accumulate,
                       const GramPlan& p, char* ws, hipStream_t stream) {
-  // workspace: [tile table | slabs | pack chunk]
-  int32_t* tile_table = reinterpret_cast<int32_t*>(ws);
-  ws += table_bytes(p);
-  TC* slabs = reinterpret_cast<TC*>(ws);
-  if (p.staging == STAGE_SMALL) {
-    constexpr int threads = 512;
-    // panel width 32 / 64 / 128 reduced columns with 32 / 16 / 8 frames per stage (see gram_small_kernel); the wider
-    // class when the stage's raw frames would not fit the registers that carry them (SM_MAXVEC 16-byte pieces per thread)
-    int width = n_red <= 32 ? 32 : (n_red <= 64 ? 64 : TILE);
-    while (width < TILE && small_raw_bytes<TIn>(N, 8 * TILE / width) / 16 - 1 > (size_t)SM_MAXVEC * threads) width *= 2;
-    if (p.nt1 == 2 || p.wide256) width = 2 * TILE;
-    if (p.nt1 > 2) width = 4 * TILE;
-    int kbs = width > 2 * TILE ? 4 : 8 * TILE / width;  // (the MFMA's K = 4 frames is the smallest stage)
-    // 256 columns: 8 frames per stage where they fit (one workgroup per CU: nothing covers a stage's barriers and group
-    // sums but its own MFMAs, and 4 frames are 15 MFMAs per wave)
-    // -- up to 5 blocks per wave (~200 columns): beyond, the longer MFMA phase spills (224 atoms 6.3 -> 9.2 ms)
-    if (width == 2 * TILE && small_raw_bytes<TIn>(N, 8) / 16 - 1 <= (size_t)5 * 1024 &&
-        ((n_red + 15) / 16) * ((n_red + 15) / 16 + 1) / 2 <= 5 * 16)
-      kbs = 8;
-    const int wt = width > TILE ? width : TILE;
-    const int n_thr = width > TILE ? 1024 : threads;
-    const size_t raw_bytes = small_raw_bytes<TIn>(N, kbs);
-    const size_t lds = (size_t)kbs * (3 * width + ROW_PAD) * sizeof(TC) + raw_bytes +
-                       (size_t)round_up(((int64_t)N + wt + 1) * 4, 16) + (size_t)3 * width * 4 * sizeof(unsigned short);
-    const int nv = (int)ceil_div((int64_t)(raw_bytes / 16 - 1), n_thr);
-    if (nv > SM_MAXVEC || (width > TILE && nv > 5)) return fail(AGGF_ERR_ARG, "aggf_gram: small-system kernel: frame too large");
-    const int nb16 = (n_red + 15) / 16, n_blocks = nb16 * (nb16 + 1) / 2;
-    const int per_part = (int)ceil_div((int64_t)n_blocks, p.parts);
-    const int per_wave = (int)ceil_div((int64_t)per_part, width > TILE ? 16 : 8);  // blocks per active wave (template C)
-#define AGGF_SMALL(NVC, KBC, NWC, WC, CC)                                                                            \
-  do {                                                                                                               \
-    if (lds > 65536) {                                                                                               \
-      static thread_local PerDeviceOnce attr_once;                                                                   \
-      bool& attr_done = *attr_once.flag();                                                                           \
-      if (!attr_done) {                                                                                              \
-        AGGF_HIP_OK(hipFuncSetAttribute((const void*)gram_small_kernel<TIn, TC, NVC, KBC, NWC, WC, CC>,              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));             \
-        attr_done = true;                                                                                            \
-      }                                                                                                              \
-    }                                                                                                                \
-    AGGF_LAUNCH((gram_small_kernel<TIn, TC, NVC, KBC, NWC, WC, CC>), dim3((unsigned)p.ksplit, (unsigned)p.parts), \
-                       dim3(64 * NWC), lds, stream, reinterpret_cast<const TIn*>(Fv), T, N, grp_ptr, grp_atoms,      \
-                       n_red, p.frames_per_split, (int32_t)raw_bytes, slabs);                                        \
-  } while (0)
-#define AGGF_SMALL_NV(KBC, WC, CC)                                                                                   \
-  do {                                                                                                               \
-    if (nv <= 3) AGGF_SMALL(3, KBC, 8, WC, CC);                                                                      \
-    else if (nv <= 5) AGGF_SMALL(5, KBC, 8, WC, CC);                                                                 \
-    else AGGF_SMALL(8, KBC, 8, WC, CC);                                                                              \
-  } while (0)
-#define AGGF_SMALL_WIDE(WC, CC)                                                                                      \
-  do {                                                                                                               \
-    if (nv <= 3) AGGF_SMALL(3, 4, 16, WC, CC);                                                                       \
-    else AGGF_SMALL(5, 4, 16, WC, CC);                                                                               \
-  } while (0)
-#define AGGF_SMALL_WIDE8(CC)                                                                                         \
-  do {                                                                                                               \
-    if (nv <= 3) AGGF_SMALL(3, 8, 16, 2 * TILE, CC);                                                                 \
-    else AGGF_SMALL(5, 8, 16, 2 * TILE, CC);                                                                         \
-  } while (0)
-    if (width == 32) AGGF_SMALL_NV(32, 32, 1);                       // 1 or 3 blocks
-    else if (width == 64 && per_wave <= 1) AGGF_SMALL_NV(16, 64, 1);  // 6 blocks
-    else if (width == 64) AGGF_SMALL_NV(16, 64, 2);                  // 10
-    else if (width == TILE && per_wave <= 2) AGGF_SMALL_NV(8, TILE, 2);   // 15
-    else if (width == TILE && per_wave == 3) AGGF_SMALL_NV(8, TILE, 3);   // 21
-    else if (width == TILE && per_wave == 4) AGGF_SMALL_NV(8, TILE, 4);   // 28
-    else if (width == TILE) AGGF_SMALL_NV(8, TILE, 5);                    // 36
-    else if (width == 2 * TILE && kbs == 8 && per_wave <= 3) AGGF_SMALL_WIDE8(3);  // 256-column panel, 16 waves, 8 frames
-    else if (width == 2 * TILE && kbs == 8 && per_wave == 4) AGGF_SMALL_WIDE8(4);
-    else if (width == 2 * TILE && kbs == 8) AGGF_SMALL_WIDE8(5);
-    else if (width == 2 * TILE && per_wave <= 3) AGGF_SMALL_WIDE(2 * TILE, 3);   // 4 frames (the frames of 8 do not fit): 45 blocks
-    else if (width == 2 * TILE && per_wave == 4) AGGF_SMALL_WIDE(2 * TILE, 4);   // 55
-    else if (width == 2 * TILE && per_wave == 5) AGGF_SMALL_WIDE(2 * TILE, 5);   // 66, 78
-    else if (width == 2 * TILE && per_wave == 6) AGGF_SMALL_WIDE(2 * TILE, 6);   // 91
-    else if (width == 2 * TILE && per_wave == 7) AGGF_SMALL_WIDE(2 * TILE, 7);   // 105
-    else if (width == 2 * TILE && per_wave == 8) AGGF_SMALL_WIDE(2 * TILE, 8);   // 120
-    else if (width == 2 * TILE) AGGF_SMALL_WIDE(2 * TILE, 9);                    // 136
-    else if (per_wave <= 6) {
-      // 512-column panel: 77 - 96 blocks per workgroup (float64 products: with float32 a workgroup has at least 97)
-      if constexpr (std::is_same<TC, float>::value) {
-        AGGF_SMALL_WIDE(4 * TILE, 7);
-      } else {
-        if (per_wave <= 5) AGGF_SMALL_WIDE(4 * TILE, 5);
-        else AGGF_SMALL_WIDE(4 * TILE, 6);
-      }
-    }
-    else if (per_wave == 7) AGGF_SMALL_WIDE(4 * TILE, 7);
-    else if (per_wave == 8) AGGF_SMALL_WIDE(4 * TILE, 8);
-    else if (per_wave == 9) AGGF_SMALL_WIDE(4 * TILE, 9);            // <= 144
-    else {
-      // float32 products only (make_plan): up to 12 blocks per wave, 192 per workgroup
-      if constexpr (std::is_same<TC, float>::value) {
-        if (per_wave == 10) AGGF_SMALL_WIDE(4 * TILE, 10);
-        else if (per_wave == 11) AGGF_SMALL_WIDE(4 * TILE, 11);
-        else AGGF_SMALL_WIDE(4 * TILE, 12);
-      } else {
-        return fail(AGGF_ERR_ARG, "aggf_gram: streaming kernel: more than 144 blocks per workgroup with float64 products");
-      }
-    }
-#undef AGGF_SMALL_WIDE
-#undef AGGF_SMALL_WIDE8
-#undef AGGF_SMALL_NV
-#undef AGGF_SMALL
-    AGGF_LAUNCH_OK();
-    if (width == 4 * TILE)
-      AGGF_LAUNCH_GATED(256, (gram_reduce_small_kernel<TC, 4 * TILE>), dim3(4 * TILE), dim3(1024), 0, stream, slabs, p.ksplit,
-                         n_red, accumulate, G, p.parts);
-    else if (width > TILE)
-      AGGF_LAUNCH_GATED(256, (gram_reduce_small_kernel<TC, 2 * TILE>), dim3(2 * TILE), dim3(4 * TILE), 0, stream, slabs, p.ksplit,
-                         n_red, accumulate, G, 1);
-    else
-      AGGF_LAUNCH_GATED(256, (gram_reduce_small_kernel<TC, TILE>), dim3(TILE), dim3(2 * TILE), 0, stream, slabs, p.ksplit, n_red,
-                         accumulate, G, 1);
+  const GramWorkspace layout = workspace_layout(p);
+  const TIn* F = reinterpret_cast<const TIn*>(Fv);
+  if (p.staging == STAGE_SMALL)
+    return launch_small_class<TIn, TC>(p, F, T, N, grp_ptr, grp_atoms, n_red, G, accumulate,
+                                       reinterpret_cast<TC*>(ws + layout.slabs), stream);
+  if (p.direct) {
+    // TIn == TC, or float32 frames widened inside the tile kernel.  straddle: all frames but the last through the tile
+    // kernel (the piece across the end of row t reads the head of row t + 1), the last one as a rank-3 update of G
+    const int64_t rows = p.straddle ? T - 1 : T, ld = (int64_t)N * 3;
+    const int rc = p.edge ? launch_gram<TC, true, TIn>(F, rows, ld, p, ws, G, n_red, accumulate, stream)
+                          : launch_gram<TC, false, TIn>(F, rows, ld, p, ws, G, n_red, accumulate, stream);
+    if (rc || !p.straddle) return rc;
+    AGGF_LAUNCH((gram_tail_row_kernel<TIn>), dim3((unsigned)ceil_div((int64_t)n_red, 16), (unsigned)ceil_div((int64_t)n_red, 16)),
+                dim3(16, 16), 0, stream, F + (T - 1) * ld, n_red, G);
     AGGF_LAUNCH_OK();
     return AGGF_OK;
   }
-  if (p.direct) {
-    // TIn == TC, or float32 frames widened inside the tile kernel
-    if (p.edge && p.straddle) {
-      // all frames but the last through the tile kernel (the piece across the end of row t reads the head of row t + 1),
-      // the last one as a rank-3 update of G
-      const TIn* F = reinterpret_cast<const TIn*>(Fv);
-      int rc = launch_gram<TC, true, TIn>(F, T - 1, (int64_t)N * 3, p, slabs, tile_table, G, n_red, accumulate, stream, true);
-      if (rc) return rc;
-      AGGF_LAUNCH((gram_tail_row_kernel<TIn>), dim3((unsigned)ceil_div((int64_t)n_red, 16), (unsigned)ceil_div((int64_t)n_red, 16)),
-                  dim3(16, 16), 0, stream, F + (T - 1) * (int64_t)N * 3, n_red, G);
-      AGGF_LAUNCH_OK();
-      return AGGF_OK;
-    }
-    if (p.edge)
-      return launch_gram<TC, true, TIn>(reinterpret_cast<const TIn*>(Fv), T, (int64_t)N * 3, p, slabs, tile_table, G,
-                                        n_red, accumulate, stream);
-    return launch_gram<TC, false, TIn>(reinterpret_cast<const TIn*>(Fv), T, (int64_t)N * 3, p, slabs, tile_table, G,
-                                       n_red, accumulate, stream);
-  }
-  TC* pack = reinterpret_cast<TC*>(ws + round_up((int64_t)p.slab_bytes, 256));
-  const TIn* F = reinterpret_cast<const TIn*>(Fv);
+  TC* pack = reinterpret_cast<TC*>(ws + layout.pack);
   // The pack pass is HBM-bound, the tile kernel MFMA-bound: the chunk is split into two half-size buffers and chunk
   // i + 1 is packed on a side stream while chunk i is multiplied; a trajectory that fits one chunk is still cut into
   // PACK_MIN_CHUNKS pieces for the same reason.  The pack beside the tile kernel is a SMALL grid of long-lived
@@ -1764,23 +1830,20 @@ static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_p
   // with the tile kernel's for the CUs and break up the cohorts that share panels in the L2.  C3 with bond pairs,
   // Gram stage (tools/pack_ab.sh): serial 404-407 ms; overlapped with the full grid 562-581; with 32 / 64 / 128 / 192 /
   // 256 / 384 / 512 workgroups 1017 / 633 / 430 / 396 / 397 / 399 / 409 -- 35 ms of pack, 8 of them hidden.
-  // AGGF_GRAM_PACK=serial: one buffer, one stream; =chunked: the overlapped form's chunks on one stream (measurements
-  // and tests).  AGGF_GRAM_PACK_MIN_FRAMES: test hook -- the smallest chunk, so that small inputs reach the pipeline.
-  // Both are read on every call (a test compares the forms inside one process).
-  const char* pack_env = getenv("AGGF_GRAM_PACK");
-  const char* min_env = getenv("AGGF_GRAM_PACK_MIN_FRAMES");
+  // GramOverrides: the serial form, the overlapped form's chunks on one stream, the smallest chunk.
+  const GramOverrides& env = p.env;
   constexpr int PACK_MIN_CHUNKS = 8;
   // a chunk must be worth its launches and event waits: >= 8192 frames and >= 4e11 flop (~6 ms of tile kernel)
   int64_t PACK_MIN_FRAMES = (int64_t)(4e11 / (3.0 * (double)p.n_pad * (double)p.n_pad)) + 1;
   if (PACK_MIN_FRAMES < 8192) PACK_MIN_FRAMES = 8192;
-  if (min_env && atoll(min_env) >= 8) PACK_MIN_FRAMES = atoll(min_env);
+  if (env.pack_min_frames >= 8) PACK_MIN_FRAMES = env.pack_min_frames;
   const size_t row_elems = (size_t)p.n_pad * 3;
   int64_t cf = p.chunk_frames;
   // (up to 1024 columns the tile kernel is short against the pack pass and the throttled pack beside it loses: 700 atoms
   // 31.0 against 27.1 ms, 1000 atoms 32.9 against 31.4 -- serial there; the min-frames hook still reaches the pipeline)
-  bool overlap = !(pack_env && pack_env[0] == 's') && T >= 2 * PACK_MIN_FRAMES && p.chunk_frames / 2 >= PACK_MIN_FRAMES &&
-                 (p.n_pad > routing::pack_overlap_min_pad || min_env);
-  const bool same_stream = pack_env && pack_env[0] == 'c';  // (measurement: the overlapped form's chunks, one stream)
+  bool overlap = !env.pack_serial && T >= 2 * PACK_MIN_FRAMES && p.chunk_frames / 2 >= PACK_MIN_FRAMES &&
+                 (p.n_pad > routing::pack_overlap_min_pad || env.pack_min_frames >= 0);
+  const bool same_stream = env.pack_one_stream;
   PackPipe* pipe = overlap ? pack_pipe() : nullptr;
   if (overlap && !pipe) overlap = false;  // no side stream: the serial form
   if (overlap) {
@@ -1796,13 +1859,9 @@ static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_p
   TC* bufs[2] = {pack, overlap ? pack + (size_t)cf * row_elems : pack};
   auto launch_pack = [&](int64_t t0, int64_t rows, TC* dst, hipStream_t st) {
     const unsigned gx = (unsigned)ceil_div((int64_t)p.n_pad * 3, 256 * PK_ELEMS);
-    int64_t gy = ceil_div((int64_t)16 * device_cu_count(), gx);  // ~16 workgroups per CU in all
-    if (st != stream) {
-      // beside the tile kernel: a FEW long-lived workgroups that trickle the chunk through (a full-size grid's
-      // workgroups take turns with the tile kernel's for the CUs and break up the cohorts that share panels in the L2):
-      // one per CU (32 / 64 / 128 / 192 / 256 / 384 / 512 workgroups: 1017 / 633 / 430 / 396 / 397 / 399 / 409 ms)
-      gy = ceil_div((int64_t)device_cu_count(), (int64_t)gx);
-    }
+    // ~16 workgroups per CU in all; beside the tile kernel (see above) a FEW long-lived workgroups that trickle the chunk
+    // through: one per CU
+    int64_t gy = ceil_div((int64_t)(st != stream ? 1 : 16) * device_cu_count(), gx);
     if (gy > rows) gy = rows;
     if (st != stream)
       AGGF_LAUNCH((pack_groups_kernel<TIn, TC, true>), dim3(gx, (unsigned)gy), dim3(256), 0, st,
@@ -1822,10 +1881,7 @@ static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_p
   for (int64_t t0 = 0; t0 < T; t0 += cf, ++i) {
     const int64_t rows = (T - t0 < cf) ? T - t0 : cf;
     const int b = (int)(i & 1);
-    if (overlap && same_stream) {
-      launch_pack(t0, rows, bufs[b], stream);
-      AGGF_LAUNCH_OK();
-    } else if (overlap) {
+    if (overlap && !same_stream) {
       if (i >= 2) AGGF_HIP_OK(hipStreamWaitEvent(pipe->side, pipe->consumed[b], 0));  // the kernel that read this buffer
       launch_pack(t0, rows, bufs[b], pipe->side);
       AGGF_LAUNCH_OK();
@@ -1835,7 +1891,7 @@ static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_p
       launch_pack(t0, rows, bufs[b], stream);
       AGGF_LAUNCH_OK();
     }
-    int rc = launch_gram<TC>(bufs[b], rows, (int64_t)p.n_pad * 3, p, slabs, tile_table, G, n_red, acc, stream);
+    int rc = launch_gram<TC>(bufs[b], rows, (int64_t)p.n_pad * 3, p, ws, G, n_red, acc, stream);
     if (rc) {
       // the side stream may still be writing the caller's workspace: join it into `stream` before handing back
       if (overlap && !same_stream && hipEventRecord(pipe->packed[b], pipe->side) == hipSuccess)
@@ -1852,31 +1908,21 @@ static int gram_typed(const void* Fv, int64_t T, int32_t N, const int32_t* grp_p
 
 using namespace aggf;
 
-static size_t gram_workspace_query(int64_t T, int32_t N, int32_t n_red, int in_dtype, int compute_dtype, bool has_groups,
-                                   int32_t first_col) {
-  if (T <= 0 || N <= 0 || n_red <= 0) return 0;
-  GramPlan p;
-  make_plan(T, N, n_red, in_dtype, compute_dtype, has_groups, true, 0, true, &p, first_col);
-  return table_bytes(p) + (size_t)round_up((int64_t)p.slab_bytes, 256) + p.pack_bytes + 1024;
-}
-
 extern "C" size_t aggf_gram_workspace_bytes(int64_t T, int32_t N, int32_t n_red, int in_dtype,
                                             int compute_dtype, int has_groups) {
-  return gram_workspace_query(T, N, n_red, in_dtype, compute_dtype, has_groups != 0, 0);
+  if (T <= 0 || N <= 0 || n_red <= 0) return 0;
+  GramPlan p;
+  make_plan({T, N, n_red, in_dtype, compute_dtype, has_groups != 0}, &p);
+  return workspace_query_bytes(p);
 }
 
-// first_col > 0 takes no straddling form: rows that are not whole 16-byte pieces with N % 128 != 0 leave the in-place
-// kernel for the pack + tile pipeline, whose pack chunk the query must plan -- sized by aggf_gram's query, which plans
-// in place, the chunks were carved out of a slab-only workspace (one pack, table, tile and reduce launch per few
-// thousand frames).  An in-place plan keeps aggf_gram's workspace and with it aggf_gram's split count: the tiles outside
-// the leading block stay bit-identical to aggf_gram's.
 extern "C" size_t aggf_gram_from_column_workspace_bytes(int64_t T, int32_t N, int32_t n_red, int in_dtype,
                                                         int compute_dtype, int32_t first_col) {
   if (first_col < 0 || first_col % TILE != 0) return 0;
   if (T <= 0 || N <= 0 || n_red <= 0) return 0;
   GramPlan p;
-  make_plan(T, N, n_red, in_dtype, compute_dtype, false, true, 0, true, &p, first_col);
-  return gram_workspace_query(T, N, n_red, in_dtype, compute_dtype, false, p.direct ? 0 : first_col);
+  make_plan({T, N, n_red, in_dtype, compute_dtype, false, first_col}, &p);
+  return workspace_query_bytes(p);
 }
 
 static int gram_impl(const void* F, int64_t T, int32_t N, int in_dtype, int compute_dtype,
@@ -1899,15 +1945,11 @@ static int gram_impl(const void* F, int64_t T, int32_t N, int in_dtype, int comp
   // would ADD) it, so the result of accumulate + first_col would depend on pointer alignment: refused
   if (first_col > 0 && accumulate) return fail(AGGF_ERR_ARG, "aggf_gram_from_column: accumulate != 0 needs first_col == 0");
   if (((uintptr_t)ws & 255) != 0) return fail(AGGF_ERR_ARG, "aggf_gram: workspace not 256-byte aligned");
-  // (the kernels take F at any element-aligned address: the launch plan does not depend on where a frame block starts,
-  // so the workspace query, which sees no pointer, always describes the plan of the call)
   if (((uintptr_t)F & (dtype_size(in_dtype) - 1)) != 0) return fail(AGGF_ERR_ARG, "aggf_gram: F is not aligned to its element size");
-  const bool aligned = true;
   GramPlan p;
-  int rc = make_plan(T, N, n_red, in_dtype, compute_dtype, has_groups, aligned, ws_bytes, false, &p, first_col);
+  int rc = make_plan({T, N, n_red, in_dtype, compute_dtype, has_groups, first_col}, ws_bytes, &p);
   if (rc) return rc;
-  if (table_bytes(p) + (size_t)round_up((int64_t)p.slab_bytes, 256) + p.pack_bytes > ws_bytes)
-    return fail(AGGF_ERR_WORKSPACE, "aggf_gram: workspace too small");
+  if (workspace_layout(p).total > ws_bytes) return fail(AGGF_ERR_WORKSPACE, "aggf_gram: workspace too small");
   char* w = reinterpret_cast<char*>(ws);
   if (in_dtype == AGGF_F64)
     return gram_typed<double, double>(F, T, N, grp_ptr, grp_atoms, n_red, G, accumulate, p, w, stream);
@@ -1922,44 +1964,28 @@ extern "C" int aggf_gram(const void* F, int64_t T, int32_t N, int in_dtype, int 
   return gram_impl(F, T, N, in_dtype, compute_dtype, grp_ptr, grp_atoms, n_red, 0, G, accumulate, ws, ws_bytes, stream_v);
 }
 
-// Gram matrix of the column-concatenation [F | F2] without materialising it: both (T, ., 3) arrays of the same dtype
-// (which is also the arithmetic type of the products), N and N2 multiples of 128, 16-byte aligned.
-template <typename T>
-static int gram_pair_typed(const T* F, const T* F2, int64_t rows, int32_t N, int32_t N2, const GramPlan& p, char* ws,
-                           double* G, int accumulate, hipStream_t stream) {
-  constexpr int KB = GramCfg<T>::KB;
-  int32_t* tile_table = reinterpret_cast<int32_t*>(ws);
-  T* slabs = reinterpret_cast<T*>(ws + table_bytes(p));
-  const int ksplit = p.ksplit;
-  int64_t fps = round_up(ceil_div(rows, ksplit), KB);
-  if (fps < KB) fps = KB;
-  const size_t lds3 = (size_t)3 * 2 * dma_panel_elems<T>() * sizeof(T);
-  static thread_local PerDeviceOnce attr_once;
-  bool& attr_done = *attr_once.flag();
-  if (!attr_done) {
-    AGGF_HIP_OK(hipFuncSetAttribute((const void*)gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-    attr_done = true;
-  }
-  AGGF_LAUNCH(build_tile_table_kernel, dim3(1), dim3(256), 0, stream, p.nt1, tile_table, 0);
-  AGGF_LAUNCH_OK();
-  const int64_t nblk = (int64_t)ksplit * p.n_tiles;
-  if (nblk > 0x7fffff00LL) return fail(AGGF_ERR_ARG, "gram grid too large");
-  AGGF_LAUNCH((gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, true>), dim3((unsigned)round_up(nblk, 512)),
-                     dim3(512), lds3, stream, F, rows, (int64_t)N * 3, p.nt1, p.n_tiles, ksplit, tile_table, fps, slabs, F2,
-                     (int64_t)N2 * 3, N / TILE);
-  AGGF_LAUNCH_OK();
-  AGGF_LAUNCH_GATED(1024, (gram_reduce_kernel<T>), dim3(p.n_tiles, TILE / 8), dim3(256), 0, stream, slabs, p.nt1, ksplit,
-                     N + N2, accumulate, G, 0);
-  AGGF_LAUNCH_OK();
-  return AGGF_OK;
+extern "C" int aggf_gram_from_column(const void* F, int64_t T, int32_t N, int in_dtype, int compute_dtype,
+                                     int32_t n_red, int32_t first_col, double* G, int accumulate, void* ws,
+                                     size_t ws_bytes, void* stream_v) {
+  return gram_impl(F, T, N, in_dtype, compute_dtype, nullptr, nullptr, n_red, first_col, G, accumulate, ws, ws_bytes,
+                   stream_v);
 }
 
 extern "C" size_t aggf_gram_pair_workspace_bytes(int64_t T, int32_t N, int32_t N2, int dtype) {
   if (T <= 0 || N <= 0 || N2 <= 0) return 0;
   GramPlan p;
-  make_plan(T, N + N2, N + N2, dtype, dtype, false, true, 0, true, &p, 0, true);
-  return table_bytes(p) + (size_t)round_up((int64_t)p.slab_bytes, 256) + p.pack_bytes + 1024;
+  make_plan({T, N + N2, N + N2, dtype, dtype, false, 0, true}, &p);
+  return workspace_query_bytes(p);
+}
+
+// Gram matrix of the column-concatenation [F | F2] without materialising it: both (T, ., 3) arrays of the same dtype
+// (which is also the arithmetic type of the products), N and N2 multiples of 128, 16-byte aligned.
+template <typename T>
+static int gram_pair_typed(const void* F, const void* F2, int64_t rows, int32_t N, int32_t N2, const GramPlan& p, char* ws,
+                           double* G, int accumulate, hipStream_t stream) {
+  return launch_tiles<gram_tile_dma_kernel<T, 0, 3, 2, 8, true, 1, true, true>, T>(
+      single_tile_shape<T>(), (const T*)F, rows, (int64_t)N * 3, p, ws, G, N + N2, accumulate, stream, (const T*)F2,
+      (int64_t)N2 * 3, (int32_t)(N / TILE), (int32_t)0, (int32_t)0);
 }
 
 extern "C" int aggf_gram_pair(const void* F, int32_t N, const void* F2, int32_t N2, int64_t T, int dtype, double* G,
@@ -1973,20 +1999,11 @@ extern "C" int aggf_gram_pair(const void* F, int32_t N, const void* F2, int32_t 
   if ((((uintptr_t)F | (uintptr_t)F2) & 15) != 0) return fail(AGGF_ERR_ARG, "aggf_gram_pair: arrays must be 16-byte aligned");
   if (((uintptr_t)ws & 255) != 0) return fail(AGGF_ERR_ARG, "aggf_gram_pair: workspace not 256-byte aligned");
   GramPlan p;
-  int rc = make_plan(T, N + N2, N + N2, dtype, dtype, false, true, ws_bytes, false, &p, 0, true);
+  int rc = make_plan({T, N + N2, N + N2, dtype, dtype, false, 0, true}, ws_bytes, &p);
   if (rc) return rc;
   if (!p.direct || p.staging == STAGE_SMALL) return fail(AGGF_ERR_ARG, "aggf_gram_pair: unsupported layout");
-  if (table_bytes(p) + (size_t)round_up((int64_t)p.slab_bytes, 256) > ws_bytes)
-    return fail(AGGF_ERR_WORKSPACE, "aggf_gram_pair: workspace too small");
+  if (workspace_layout(p).total > ws_bytes) return fail(AGGF_ERR_WORKSPACE, "aggf_gram_pair: workspace too small");
   char* w = reinterpret_cast<char*>(ws);
-  if (dtype == AGGF_F64)
-    return gram_pair_typed<double>((const double*)F, (const double*)F2, T, N, N2, p, w, G, accumulate, stream);
-  return gram_pair_typed<float>((const float*)F, (const float*)F2, T, N, N2, p, w, G, accumulate, stream);
-}
-
-extern "C" int aggf_gram_from_column(const void* F, int64_t T, int32_t N, int in_dtype, int compute_dtype,
-                                     int32_t n_red, int32_t first_col, double* G, int accumulate, void* ws,
-                                     size_t ws_bytes, void* stream_v) {
-  return gram_impl(F, T, N, in_dtype, compute_dtype, nullptr, nullptr, n_red, first_col, G, accumulate, ws, ws_bytes,
-                   stream_v);
+  if (dtype == AGGF_F64) return gram_pair_typed<double>(F, F2, T, N, N2, p, w, G, accumulate, stream);
+  return gram_pair_typed<float>(F, F2, T, N, N2, p, w, G, accumulate, stream);
 }

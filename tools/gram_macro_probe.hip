@@ -24,13 +24,11 @@ struct Probe {
 
 template <typename FORM>
 static void run_form(Probe& pr, const char* name) {
-  int32_t* table = reinterpret_cast<int32_t*>(pr.ws);
-  double* slabs = reinterpret_cast<double*>(pr.ws + table_bytes(pr.plan));
   float best = 1e30f;
   int rc = 0;
   for (int rep = 0; rep < pr.reps + 1 && rc == 0; ++rep) {
     hipEventRecord(pr.e0);
-    rc = launch_gram_macro<FORM>(pr.F, pr.T, (int64_t)pr.N * 3, pr.plan, slabs, table, pr.G, pr.N, 0, nullptr);
+    rc = launch_gram_macro<FORM>(pr.F, pr.T, (int64_t)pr.N * 3, pr.plan, pr.ws, pr.G, pr.N, 0, nullptr);
     hipEventRecord(pr.e1);
     if (hipEventSynchronize(pr.e1) != hipSuccess) rc = -1;
     float ms = 0.f;
@@ -99,7 +97,7 @@ int main(int argc, char** argv) {
          (long long)T, rc, best);
   fflush(stdout);
 
-  if (make_plan(T, N, N, AGGF_F64, AGGF_F64, false, true, need, false, &pr.plan) != 0 || !pr.plan.macro) {
+  if (make_plan({T, N, N, AGGF_F64, AGGF_F64, false}, need, &pr.plan) != 0 || !pr.plan.macro) {
     printf("{\"error\": \"no macro-tile plan for %d tile rows\"}\n", nt1);
     return 1;
   }
