@@ -1,4 +1,5 @@
-"""Differentiable map application and pair distances: eight ``torch.autograd.Function``s over the HIP kernels.
+"""Differentiable map application, pair distances and radial basis: ten ``torch.autograd.Function``s over the HIP
+kernels.
 
 Each Function is one kernel launch; the backward of each calls only these same Functions, so the set is closed under
 differentiation (``gradgradcheck``, force-matching double backward).  Shapes: points (T, N, 3), a 2-D map (n_cg, N),
@@ -26,6 +27,19 @@ PairPull(W, X, C) -> A, B   A[t,j] = sum_i W_ij u_ij, B[t,i] = -sum_j (K9b)  dW 
                                                                              (dX, dC) = PairPull(W, GA, GB)
 PairDot(V, Y, X, C)         out[t,i,j] = (V[t,j] - Y[t,i]).u          (K9a)  (dV, dY) = PairPull(H, X, C),
                                                                              (dX, dC) = PairPull(H, V, Y)
+==========================  ===============================================  ==========================================
+
+The Gaussian radial basis (``qp.jaxfeat``): distances D of any shape, g_k^(q) the q-th derivative of the clipped
+Gaussian of centre k (q = 0: the value; q at run time, by the Hermite recurrence), col0(e) = 0, or with channel slots
+slot(site of e) * n_basis in a row of n_slots * n_basis values.  ``collapse``: the sum over all elements of a slot.
+
+==========================  ===============================================  ==========================================
+Function                    forward                                          backward (upstream H, or G)
+==========================  ===============================================  ==========================================
+Basis(S, D, q)              out[e, col0 + k] = S[e] g_k^(q)(D[e])    (K10a)  dS = BasisDot(H, D, q),
+                            collapse: out[slot, k] = sum_e of that   (K10c)  dD = S * BasisDot(H, D, q + 1)
+BasisDot(H, D, q)           out[e] = sum_k H[., k] g_k^(q)(D[e])     (K10b)  dH = Basis(G, D, q),
+                            H per element, slotted row or slot table         dD = G * BasisDot(H, D, q + 1)
 ==========================  ===============================================  ==========================================
 
 A zero distance has weight 0: torch's own first-order value at |0|, and what keeps every higher order finite (the
@@ -267,3 +281,56 @@ class PairDot(torch.autograd.Function):
         if need[2] or need[3]:
             dX, dC = PairPull.apply(H, V, Y, need[2], need[3], _pull_dtype(ct, X, C, need[2], need[3]))
         return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype)
+
+
+# ------------------------------------------------------------------ Gaussian radial basis (K10)
+def _basis_form(spec: "K.BasisSpec", collapse: bool) -> int:
+    return K.GB_H_SLOT if collapse else (K.GB_H_ROW if spec.slot is not None else K.GB_H_ELEM)
+
+
+class Basis(torch.autograd.Function):
+    """out[e, col0(e) + k] = S[e] g_k^(q)(D[e]) on K10a (``aggf_gbasis_expand``), D.shape + (row,); ``collapse``:
+    summed over the elements of each slot on K10c (``aggf_gbasis_sum``), (n_slots, n_basis).  ``S`` None: 1.  ``spec``:
+    a ``_kernels.BasisSpec`` in the dtype and on the device of D (centres, width, clip, slots: constants)."""
+
+    @staticmethod
+    def forward(ctx, S, D, q, spec, collapse=False):
+        d = D.contiguous()
+        s = None if S is None else _widened(S, D.dtype)
+        ctx.q, ctx.spec, ctx.collapse = int(q), spec, bool(collapse)
+        ctx.save_for_backward(S, D)
+        return K.gbasis_sum(d, spec, q, s) if collapse else K.gbasis_expand(d, spec, q, s)
+
+    @staticmethod
+    def backward(ctx, H):
+        S, D = ctx.saved_tensors
+        dS = dD = None
+        if S is not None and ctx.needs_input_grad[0]:
+            dS = _as(BasisDot.apply(H, D, ctx.q, ctx.spec, ctx.collapse), S.dtype)
+        if ctx.needs_input_grad[1]:
+            dD = BasisDot.apply(H, D, ctx.q + 1, ctx.spec, ctx.collapse)
+            if S is not None:
+                dD = S * dD
+            dD = _as(dD, D.dtype)
+        return dS, dD, None, None, None
+
+
+class BasisDot(torch.autograd.Function):
+    """out[e] = sum_k H[., k] g_k^(q)(D[e]) on K10b (``aggf_gbasis_contract``), D.shape; H in the layout of the
+    ``Basis`` output of the same ``spec`` / ``collapse``: per element, per slotted row, or the (n_slots, n_basis) table."""
+
+    @staticmethod
+    def forward(ctx, H, D, q, spec, collapse=False):
+        ctx.q, ctx.spec, ctx.collapse = int(q), spec, bool(collapse)
+        ctx.save_for_backward(H, D)
+        return K.gbasis_contract(_widened(H, D.dtype), D.contiguous(), spec, q, _basis_form(spec, collapse))
+
+    @staticmethod
+    def backward(ctx, G):
+        H, D = ctx.saved_tensors
+        dH = dD = None
+        if ctx.needs_input_grad[0]:
+            dH = _as(Basis.apply(G, D, ctx.q, ctx.spec, ctx.collapse), H.dtype)
+        if ctx.needs_input_grad[1]:
+            dD = _as(G * BasisDot.apply(H, D, ctx.q + 1, ctx.spec, ctx.collapse), D.dtype)
+        return dH, dD, None, None, None

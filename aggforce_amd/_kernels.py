@@ -1214,3 +1214,131 @@ def pair_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, dv: Optional[to
         check(l.aggf_pair_pull(ptr(w), ptr(dv), ptr(x), ptr(c), T, m, n, dtype_code(x.dtype), ptr(a), ptr(b),
                                dtype_code(out_dtype), ptr(ws), need, stream_ptr()), "aggf_pair_pull")
     return a, b
+
+
+# ------------------------------------------------------------------ K10 Gaussian radial basis (aggforce_amd/_autograd.py)
+GB_H_ELEM, GB_H_ROW, GB_H_SLOT = 0, 1, 2
+
+
+class BasisSpec:
+    """The constants of one Gaussian basis on one device: ``centers`` (n_basis,) in the dtype of the distances, ``width``
+    and ``clip`` (None: no clipping, the arithmetic of clip = 0), and optionally the channel slots of the sites
+    (``channels``: one integer per site; a channel outside [0, n_slots) is dropped).  ``order`` / ``start``: the kept
+    sites sorted by slot and each slot's range in that list (what the channel sum walks)."""
+
+    def __init__(self, centers: torch.Tensor, width: float, clip: Optional[float], channels=None,
+                 n_slots: Optional[int] = None):
+        if centers.dim() != 1 or centers.numel() < 1 or centers.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"BasisSpec: centers {tuple(centers.shape)} {centers.dtype}")
+        self.centers = centers.contiguous()
+        self.n_basis = int(centers.numel())
+        self.width = float(width)
+        self.clip = 0.0 if clip is None else float(clip)
+        if not self.width > 0 or not self.clip >= 0:
+            raise ValueError(f"BasisSpec: width {width} must be positive and clip {clip} non-negative")
+        self.slot = self.order = self.start = None
+        self.n_sites, self.n_slots, self.n_order = 1, 1, 0
+        if channels is not None:
+            ch = np.asarray(channels, dtype=np.int64).reshape(-1)
+            self.n_sites, self.n_slots = int(ch.size), int(n_slots)
+            if self.n_sites < 1 or self.n_slots < 1:
+                raise ValueError(f"BasisSpec: {self.n_sites} sites in {self.n_slots} slots")
+            kept = (ch >= 0) & (ch < self.n_slots)
+            slot = np.where(kept, ch, -1).astype(np.int32)
+            order = np.flatnonzero(kept)
+            order = order[np.argsort(slot[order], kind="stable")].astype(np.int32)
+            start = np.zeros(self.n_slots + 1, dtype=np.int32)
+            start[1:] = np.cumsum(np.bincount(slot[order], minlength=self.n_slots))
+            dev = centers.device
+            self.slot = torch.from_numpy(slot).to(dev)
+            self.order = torch.from_numpy(order if order.size else np.zeros(1, np.int32)).to(dev)
+            self.n_order = int(order.size)
+            self.start = torch.from_numpy(start).to(dev)
+
+    @property
+    def row(self) -> int:
+        return self.n_slots * self.n_basis
+
+
+def _basis_operand(name: str, x: Optional[torch.Tensor], spec: BasisSpec, shape=None) -> None:
+    if x is None:
+        return
+    if x.dtype != spec.centers.dtype or x.device != spec.centers.device or not x.is_contiguous():
+        raise ValueError(f"{name}: {tuple(x.shape)} {x.dtype} on {x.device} (contiguous, {spec.centers.dtype}, "
+                         f"on {spec.centers.device})")
+    if shape is not None and tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {tuple(shape)}")
+
+
+def _basis_sites(name: str, d: torch.Tensor, spec: BasisSpec) -> None:
+    if spec.slot is not None and (d.dim() < 1 or d.shape[-1] != spec.n_sites):
+        raise ValueError(f"{name}: distances {tuple(d.shape)} for {spec.n_sites} sites with channels")
+
+
+def gbasis_expand(d: torch.Tensor, spec: BasisSpec, q: int = 0, s: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d.shape + (row,): out[e, col0(e) + k] = s[e] g_k^(q)(d[e]) (aggf_gbasis_expand); row = n_basis, or with slots
+    n_slots * n_basis with zeros outside the site's block (the last axis of d is then the site axis)."""
+    _basis_operand("gbasis_expand: d", d, spec)
+    _basis_operand("gbasis_expand: s", s, spec, d.shape)
+    _basis_sites("gbasis_expand", d, spec)
+    out = torch.empty(tuple(d.shape) + (spec.row,), dtype=d.dtype, device=d.device)
+    if out.numel() == 0:
+        return out
+    with _timed("gbasis_expand"):
+        check(lib().aggf_gbasis_expand(ptr(d), ptr(s), ptr(spec.centers), ptr(spec.slot), d.numel(), spec.n_basis,
+                                       spec.n_sites, spec.n_slots, spec.width, spec.clip, int(q),
+                                       dtype_code(d.dtype), ptr(out), stream_ptr()), "aggf_gbasis_expand")
+    return out
+
+
+def gbasis_contract(h: torch.Tensor, d: torch.Tensor, spec: BasisSpec, q: int = 0, form: int = GB_H_ELEM) -> torch.Tensor:
+    """d.shape: out[e] = sum_k h[e][k] g_k^(q)(d[e]) (aggf_gbasis_contract); h is d.shape + (n_basis,) (GB_H_ELEM),
+    d.shape + (n_slots * n_basis,) (GB_H_ROW) or (n_slots, n_basis) (GB_H_SLOT)."""
+    _basis_operand("gbasis_contract: d", d, spec)
+    if form == GB_H_ELEM:
+        want = tuple(d.shape) + (spec.n_basis,)
+    elif form == GB_H_ROW and spec.slot is not None:
+        want = tuple(d.shape) + (spec.row,)
+    elif form == GB_H_SLOT:
+        want = (spec.n_slots, spec.n_basis)
+    else:
+        raise ValueError(f"gbasis_contract: form {form}")
+    _basis_operand("gbasis_contract: h", h, spec, want)
+    if form != GB_H_ELEM:
+        _basis_sites("gbasis_contract", d, spec)
+    out = torch.empty_like(d)
+    if out.numel() == 0:
+        return out
+    slot = None if form == GB_H_ELEM else spec.slot
+    n_sites = spec.n_sites if slot is not None else 1
+    with _timed("gbasis_contract"):
+        check(lib().aggf_gbasis_contract(ptr(h), form, ptr(d), ptr(spec.centers), ptr(slot), d.numel(), spec.n_basis,
+                                         n_sites, spec.n_slots, spec.width, spec.clip, int(q), dtype_code(d.dtype),
+                                         ptr(out), stream_ptr()), "aggf_gbasis_contract")
+    return out
+
+
+def gbasis_sum(d: torch.Tensor, spec: BasisSpec, q: int = 0, s: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n_slots, n_basis): out[slot, k] = sum over the frames and the slot's sites of s g_k^(q)(d) (aggf_gbasis_sum);
+    d (..., n_sites) with slots, any shape without (one slot).  The one-hot array is never formed."""
+    _basis_operand("gbasis_sum: d", d, spec)
+    _basis_operand("gbasis_sum: s", s, spec, d.shape)
+    _basis_sites("gbasis_sum", d, spec)
+    out = torch.empty((spec.n_slots, spec.n_basis), dtype=d.dtype, device=d.device)
+    if spec.slot is not None:
+        N = spec.n_sites
+        T = d.numel() // N
+        order, start, n_order = spec.order, spec.start, spec.n_order
+    else:  # one slot of all elements
+        N = d.shape[-1] if d.dim() else 1
+        T = d.numel() // N if N else 0
+        order = start = None
+        n_order = 0
+    l = lib()
+    need = l.aggf_gbasis_sum_workspace_bytes(T, spec.n_slots, spec.n_basis)
+    ws = workspace(need, d.device, "gbasis") if need else None
+    with _timed("gbasis_sum"):
+        check(l.aggf_gbasis_sum(ptr(d), ptr(s), ptr(spec.centers), ptr(order), ptr(start), n_order, T, N, spec.n_slots,
+                                spec.n_basis, spec.width, spec.clip, int(q), dtype_code(d.dtype), ptr(out), ptr(ws),
+                                need, stream_ptr()), "aggf_gbasis_sum")
+    return out

@@ -320,6 +320,61 @@ int main() {
                                     sel & 2 ? d + 4096 : nullptr, od, ws, wpl, nullptr));
         }
       }
+  // K10: the partials' size over the grid of shapes (absurd ones give 0), refusals (NULL pointers, bad dtype / width /
+  // clip / order / form, rows or outputs that do not fit, slot tables that do not match the form, short or misaligned
+  // workspaces), empty shapes, and plausible calls in every dtype / form / slot selection with the queried workspace
+  for (int64_t T : Ts)
+    for (int32_t N : Ns) sink += aggf_gbasis_sum_workspace_bytes(T, N, 10) + aggf_gbasis_sum_workspace_bytes(T, 600, N / 97 + 1);
+  sink += aggf_gbasis_sum_workspace_bytes(INT64_MAX, INT32_MAX, INT32_MAX) + aggf_gbasis_sum_workspace_bytes(-1, 4, 4) +
+          aggf_gbasis_sum_workspace_bytes(10, 0, 4);
+  REFUSED(aggf_gbasis_expand(p, nullptr, nullptr, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr));      // centres
+  REFUSED(aggf_gbasis_expand(nullptr, nullptr, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr));
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 1, nullptr, nullptr));
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 2, d, nullptr));            // dtype
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 0, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr));             // n_basis
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 10, 1, 1, 0.0, 1e-3, 0, 1, d, nullptr));            // width
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 10, 1, 1, 1.0, -1.0, 0, 1, d, nullptr));            // clip
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, -1, 1, d, nullptr));           // order
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 65, 1, d, nullptr));
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, -1, 10, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr));
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, i32, 70, 10, 8, 4, 1.0, 1e-3, 0, 1, d, nullptr));                // 70 % 8
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, i32, 70, 10, 7, 0, 1.0, 1e-3, 0, 1, d, nullptr));                // n_slots
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, i32, 70, 1 << 20, 7, 1 << 20, 1.0, 1e-3, 0, 1, d, nullptr));     // row
+  REFUSED(aggf_gbasis_expand(p, nullptr, p, nullptr, INT64_MAX / 4, 10, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr)); // E n_basis
+  RUNS(aggf_gbasis_expand(nullptr, nullptr, p, nullptr, 0, 10, 1, 1, 1.0, 0.0, 3, 0, nullptr, nullptr));
+  REFUSED(aggf_gbasis_contract(nullptr, AGGF_GB_H_ELEM, p, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr));
+  REFUSED(aggf_gbasis_contract(p, 3, p, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 1, d, nullptr));             // form
+  REFUSED(aggf_gbasis_contract(p, AGGF_GB_H_ROW, p, p, nullptr, 70, 10, 7, 4, 1.0, 1e-3, 0, 1, d, nullptr)); // no table
+  REFUSED(aggf_gbasis_contract(p, AGGF_GB_H_SLOT, p, p, nullptr, 70, 10, 7, 4, 1.0, 1e-3, 0, 1, d, nullptr));
+  REFUSED(aggf_gbasis_contract(p, AGGF_GB_H_SLOT, p, p, i32, 70, 10, 8, 4, 1.0, 1e-3, 0, 1, d, nullptr));    // 70 % 8
+  REFUSED(aggf_gbasis_contract(p, AGGF_GB_H_ROW, p, p, i32, 70, 1 << 20, 7, 1 << 20, 1.0, 1e-3, 0, 1, d, nullptr));
+  REFUSED(aggf_gbasis_contract(p, AGGF_GB_H_ELEM, p, p, nullptr, 70, 10, 1, 1, 1.0, 1e-3, 0, 1, nullptr, nullptr));
+  RUNS(aggf_gbasis_contract(nullptr, AGGF_GB_H_ELEM, nullptr, p, nullptr, 0, 10, 1, 1, 1.0, 1e-3, 2, 1, nullptr, nullptr));
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, i32, nullptr, 5, 10, 7, 4, 10, 1.0, 1e-3, 0, 1, d, ws, WS, nullptr));   // no start
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, nullptr, nullptr, 0, 10, 7, 4, 10, 1.0, 1e-3, 0, 1, d, ws, WS, nullptr));
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, i32, i32, 8, 10, 7, 4, 10, 1.0, 1e-3, 0, 1, d, ws, WS, nullptr));       // n_order > N
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, i32, i32, 5, 10, 7, 4, 10, 1.0, 1e-3, 0, 1, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, i32, i32, 5, 10, 7, 4, 10, 1.0, 1e-3, 0, 1, d, ws, 0, nullptr));
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, i32, i32, 5, 10, 7, 4, 10, 1.0, 1e-3, 0, 1, d, (char*)ws + 4, WS - 4, nullptr));
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, i32, i32, 5, 10, 7, 1 << 24, 10, 1.0, 1e-3, 0, 1, d, ws, WS, nullptr));  // grid.y
+  REFUSED(aggf_gbasis_sum(p, nullptr, p, nullptr, nullptr, 0, INT64_MAX / 2, 7, 1, 10, 1.0, 1e-3, 0, 1, d, ws, WS, nullptr));
+  RUNS(aggf_gbasis_sum(nullptr, nullptr, p, nullptr, nullptr, 0, 0, 7, 1, 10, 1.0, 1e-3, 0, 1, d, nullptr, 0, nullptr));  // zeros
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)2000, (int64_t)100000})
+    for (int32_t N : {1, 65, 257, 1024})
+      for (int32_t nb : {1, 10, 17})
+        for (int dt = 0; dt < 2; ++dt)
+          for (int32_t q : {0, 3}) {
+            const int32_t n_slots = N / 2 + 1;
+            RUNS(aggf_gbasis_expand(p, nullptr, p, nullptr, T * N, nb, 1, 1, 1.3, 1e-3, q, dt, d, nullptr));
+            RUNS(aggf_gbasis_expand(p, p, p, i32, T * N, nb, N, n_slots, 1.3, 0.0, q, dt, d, nullptr));
+            RUNS(aggf_gbasis_contract(p, AGGF_GB_H_ELEM, p, p, nullptr, T * N, nb, 1, 1, 1.3, 1e-3, q, dt, d, nullptr));
+            RUNS(aggf_gbasis_contract(p, AGGF_GB_H_ROW, p, p, i32, T * N, nb, N, n_slots, 1.3, 1e-3, q, dt, d, nullptr));
+            RUNS(aggf_gbasis_contract(p, AGGF_GB_H_SLOT, p, p, i32, T * N, nb, N, n_slots, 1.3, 1e-3, q, dt, d, nullptr));
+            RUNS(aggf_gbasis_contract(p, AGGF_GB_H_SLOT, p, p, nullptr, T * N, nb, N, 1, 1.3, 1e-3, q, dt, d, nullptr));
+            const size_t wg = aggf_gbasis_sum_workspace_bytes(T, n_slots, nb), w1 = aggf_gbasis_sum_workspace_bytes(T, 1, nb);
+            if (wg <= WS) RUNS(aggf_gbasis_sum(p, p, p, i32, i32, N, T, N, n_slots, nb, 1.3, 1e-3, q, dt, d, ws, wg, nullptr));
+            if (w1 <= WS) RUNS(aggf_gbasis_sum(p, nullptr, p, nullptr, nullptr, 0, T, N, 1, nb, 1.3, 1e-3, q, dt, d, ws, w1, nullptr));
+          }
   free(raw);
   printf("%d calls, %d unexpected statuses\n", n_calls, n_bad);
   return n_bad ? 1 : 0;

@@ -478,6 +478,53 @@ int aggf_pair_pull(const void* W, const void* Dv, const void* X, const void* C, 
                    void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K10  The clipped Gaussian radial basis of qp/jaxfeat.py and its derivatives of any order
+ * (the autograd Functions Basis / BasisDot of aggforce_amd/_autograd.py; reference
+ * jaxfeat.py:187-567, which JAX differentiates itself).  With z = (r - c_k) / width and
+ * e_k = exp(-z^2), for the n_basis centres c_k (`centers`, a device array in `dtype`):
+ *     g_k^(0)(r) = max(e_k, clip) - clip                       (clip = 0: no clipping)
+ *     g_k^(q)(r) = (-1/width)^q H_q(z) e_k  where e_k > clip, else 0          (q >= 1)
+ * H_q: the physicists' Hermite polynomial, by its recurrence; q (0..64) is a run-time argument,
+ * and so is n_basis (no cap).  At the tie e_k == clip the derivative is 0.  float32 uses the
+ * hardware exponential, float64 the double-precision routine.  All arrays of one call share
+ * `dtype`; base addresses need only element alignment; element offsets are 64-bit.  No atomics,
+ * fixed summation orders: bit-identical run to run.
+ *
+ * Slots (the one-hot channels of channel_allocate): `slot` is an int32 device array of n_sites
+ * entries, the elements e = 0..E-1 are (frame, site) pairs with the site fastest (E a multiple
+ * of n_sites).  A slot outside [0, n_slots) is dropped: it contributes zeros.
+ *
+ * K10a, the expand entry point: out[e, col0(e) + k] = s[e] * g_k^(q)(d[e])   (s may be NULL: 1)
+ *   slot == NULL: out (E, n_basis), col0 = 0.  Else out (E, n_slots * n_basis), col0 =
+ *   slot[site] * n_basis, zeros everywhere else in the row.  out is written once, never read.
+ * K10b, the contract entry point: out[e] = sum_k h[e][k] * g_k^(q)(d[e]), the n_basis coefficients h[e] by `form`:
+ *     AGGF_GB_H_ELEM   H (E, n_basis)                     h[e] = H[e, :]
+ *     AGGF_GB_H_ROW    H (E, n_slots * n_basis)           h[e] = H[e, col0(e) : col0(e) + n_basis]
+ *     AGGF_GB_H_SLOT   H (n_slots, n_basis)               h[e] = H[slot[site], :]   (slot == NULL: one slot)
+ *   out[e] = 0 for a dropped slot.
+ * K10c, the sum entry point: out[sl, k] = sum_t sum_{a in slot sl} s[t,a] * g_k^(q)(d[t,a]),
+ *   d and s (T, N), out (n_slots, n_basis) in `dtype`.  The sites of slot sl are
+ *   order[start[sl]] .. order[start[sl + 1] - 1] (int32 device arrays of n_order <= N and
+ *   n_slots + 1 entries; both NULL: one slot holding all N sites).  Frames are split over
+ *   workgroups, summed in float64 into ws, and the partials added in ascending order; ws_bytes >=
+ *   the query's value.  No (T, N, n_slots * n_basis) array is formed.
+ * ------------------------------------------------------------------------- */
+#define AGGF_GB_H_ELEM 0
+#define AGGF_GB_H_ROW 1
+#define AGGF_GB_H_SLOT 2
+int aggf_gbasis_expand(const void* d, const void* s, const void* centers, const int32_t* slot, int64_t E,
+                       int32_t n_basis, int32_t n_sites, int32_t n_slots, double width, double clip,
+                       int32_t q, int dtype, void* out, void* stream);
+int aggf_gbasis_contract(const void* H, int form, const void* d, const void* centers, const int32_t* slot,
+                         int64_t E, int32_t n_basis, int32_t n_sites, int32_t n_slots, double width,
+                         double clip, int32_t q, int dtype, void* out, void* stream);
+size_t aggf_gbasis_sum_workspace_bytes(int64_t T, int32_t n_slots, int32_t n_basis);
+int aggf_gbasis_sum(const void* d, const void* s, const void* centers, const int32_t* order,
+                    const int32_t* start, int32_t n_order, int64_t T, int32_t N, int32_t n_slots,
+                    int32_t n_basis, double width, double clip, int32_t q, int dtype, void* out, void* ws,
+                    size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K4b/K4c  Dense-featuriser contractions of qp_feat_linear_map (any featuriser that
  * follows the reference's protocol: feats (T, N, n_feat), divs (T, n_feat, 3) per site).
  *
