@@ -1,4 +1,4 @@
-"""Differentiable map application, pair distances and radial basis: ten ``torch.autograd.Function``s over the HIP
+"""Differentiable map application, pair distances and radial basis: thirteen ``torch.autograd.Function``s over the HIP
 kernels.
 
 Each Function is one kernel launch; the backward of each calls only these same Functions, so the set is closed under
@@ -27,6 +27,19 @@ PairPull(W, X, C) -> A, B   A[t,j] = sum_i W_ij u_ij, B[t,i] = -sum_j (K9b)  dW 
                                                                              (dX, dC) = PairPull(W, GA, GB)
 PairDot(V, Y, X, C)         out[t,i,j] = (V[t,j] - Y[t,i]).u          (K9a)  (dV, dY) = PairPull(H, X, C),
                                                                              (dX, dC) = PairPull(H, V, Y)
+==========================  ===============================================  ==========================================
+
+The same three over a static list of P pairs (i_p, j_p) shared by all frames (``jaxutil.pair_distances``; the upper
+triangles of ``jaxutil.distances`` are the list ``triu_indices``): u[t,p] = X[t,j_p] - C[t,i_p], pair arrays (T, P),
+``plist`` a ``jaxutil.PairList`` (a constant).  Nothing of size T m n is formed, forward or backward.
+
+==========================  ===============================================  ==========================================
+PairListDist(X, C, plist,   D[t,p] = |u| or u.u                       (K9c)  as PairDist, through PairListPull
+  square)
+PairListPull(W, X, C,       A[t,j] = sum_{p: j_p = j} W_p u_p,               dW = PairListDot(GA, GB, X, C),
+  plist) -> A, B            B[t,i] = -sum_{p: i_p = i} W_p u_p        (K9d)  (dX, dC) = PairListPull(W, GA, GB)
+PairListDot(V, Y, X, C,     out[t,p] = (V[t,j_p] - Y[t,i_p]).u        (K9c)  (dV, dY) = PairListPull(H, X, C),
+  plist)                                                                     (dX, dC) = PairListPull(H, V, Y)
 ==========================  ===============================================  ==========================================
 
 The Gaussian radial basis (``qp.jaxfeat``): distances D of any shape, g_k^(q) the q-th derivative of the clipped
@@ -281,6 +294,104 @@ class PairDot(torch.autograd.Function):
         if need[2] or need[3]:
             dX, dC = PairPull.apply(H, V, Y, need[2], need[3], _pull_dtype(ct, X, C, need[2], need[3]))
         return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype)
+
+
+# ------------------------------------------------------------------ pair lists (K9c / K9d)
+def _tables(plist, like: torch.Tensor) -> "K.PairTables":
+    """The device tables of ``plist`` (a ``jaxutil.PairList``, or its ``_kernels.PairTables`` already)."""
+    return plist.on(like.device) if hasattr(plist, "on") else plist
+
+
+class PairListDist(torch.autograd.Function):
+    """D[t,p] = |X[t,j_p] - C[t,i_p]| (``square``: squared) over the pairs of ``plist`` on K9c
+    (``aggf_pair_list_dist``), in the promoted dtype.  The backward is PairDist's with the list forms."""
+
+    @staticmethod
+    def forward(ctx, X, C, plist, square=False):
+        ct = _pair_dtype(X, C)
+        D = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_SQDIST if square else K.PAIR_DIST)
+        ctx.square, ctx.plist = bool(square), plist
+        ctx.save_for_backward(X, C, D)
+        return D
+
+    @staticmethod
+    def backward(ctx, H):
+        X, C, D = ctx.saved_tensors
+        plist = ctx.plist
+        want_x, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_x or want_c):
+            return None, None, None, None
+        if ctx.square:
+            dX, dC = PairListPull.apply(H, 2 * X, 2 * C, plist, want_x, want_c,
+                                        _pull_dtype(D.dtype, X, C, want_x, want_c))
+        elif torch.is_grad_enabled():
+            pos = D > 0
+            W = torch.where(pos, H / torch.where(pos, D, torch.ones_like(D)), torch.zeros_like(D))
+            dX, dC = PairListPull.apply(W, X, C, plist, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c))
+        else:
+            ct = _pair_dtype(H, D)
+            dX, dC = K.pair_list_pull(_widened(H, ct), _widened(X, ct), _widened(C, ct), _tables(plist, X),
+                                      dv=_widened(D, ct), want_a=want_x, want_b=want_c,
+                                      out_dtype=_pull_dtype(ct, X, C, want_x, want_c))
+        return _as(dX, X.dtype), _as(dC, C.dtype), None, None
+
+
+class PairListPull(torch.autograd.Function):
+    """(A, B), A[t,j,:] = sum_{p: j_p = j} W[t,p] u[t,p] and B[t,i,:] = -sum_{p: i_p = i} W[t,p] u[t,p], on K9d
+    (``aggf_pair_list_pull``), in ``out_dtype`` (default: promoted).  ``want_a`` / ``want_b`` False: that output is
+    None."""
+
+    @staticmethod
+    def forward(ctx, W, X, C, plist, want_a=True, want_b=True, out_dtype=None):
+        ct = _pair_dtype(W, X, C) if out_dtype is None else torch.promote_types(_pair_dtype(W, X, C), out_dtype)
+        A, B = K.pair_list_pull(_widened(W, ct), _widened(X, ct), _widened(C, ct), _tables(plist, X), want_a=want_a,
+                                want_b=want_b, out_dtype=out_dtype or ct)
+        ctx.plist = plist
+        ctx.save_for_backward(W, X, C)
+        return A, B
+
+    @staticmethod
+    def backward(ctx, GA, GB):
+        W, X, C = ctx.saved_tensors
+        plist = ctx.plist
+        dW = dX = dC = None
+        if GA is None and GB is None:
+            return None, None, None, None, None, None, None
+        ct = _pair_dtype(W, X, C, *(g for g in (GA, GB) if g is not None))
+        GA, GB = _zeros_if_none(GA, X, ct), _zeros_if_none(GB, C, ct)
+        if ctx.needs_input_grad[0]:
+            dW = _as(PairListDot.apply(GA, GB, X, C, plist), W.dtype)
+        want_x, want_c = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if want_x or want_c:
+            dX, dC = PairListPull.apply(W, GA, GB, plist, want_x, want_c, _pull_dtype(ct, X, C, want_x, want_c))
+        return dW, _as(dX, X.dtype), _as(dC, C.dtype), None, None, None, None
+
+
+class PairListDot(torch.autograd.Function):
+    """out[t,p] = (V[t,j_p] - Y[t,i_p]) . (X[t,j_p] - C[t,i_p]) on K9c (``aggf_pair_list_dist``, DOT), in the promoted
+    dtype."""
+
+    @staticmethod
+    def forward(ctx, V, Y, X, C, plist):
+        ct = _pair_dtype(V, Y, X, C)
+        out = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_DOT, _widened(V, ct),
+                               _widened(Y, ct))
+        ctx.plist = plist
+        ctx.save_for_backward(V, Y, X, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, H):
+        V, Y, X, C = ctx.saved_tensors
+        plist = ctx.plist
+        need = ctx.needs_input_grad
+        dV = dY = dX = dC = None
+        ct = _pair_dtype(H, V, Y, X, C)
+        if need[0] or need[1]:
+            dV, dY = PairListPull.apply(H, X, C, plist, need[0], need[1], _pull_dtype(ct, V, Y, need[0], need[1]))
+        if need[2] or need[3]:
+            dX, dC = PairListPull.apply(H, V, Y, plist, need[2], need[3], _pull_dtype(ct, X, C, need[2], need[3]))
+        return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype), None
 
 
 # ------------------------------------------------------------------ Gaussian radial basis (K10)

@@ -1216,6 +1216,76 @@ def pair_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, dv: Optional[to
     return a, b
 
 
+# ------------------------------------------------------------------ K9c / K9d pair lists (aggforce_amd/_autograd.py)
+class PairTables:
+    """A pair list on one device (built by ``jaxutil.PairList``): ``pairs`` (P, 2) int32, row p = (i_p, j_p), and the
+    two incidence tables in CSR form, by j over ``n`` sites (``a_ptr`` (n + 1,), ``a_idx`` (P,)) and by i over ``m``
+    sites (``b_ptr``, ``b_idx``), entries in ascending pair index; ``max_deg_a`` / ``max_deg_b``: their longest runs."""
+
+    def __init__(self, pairs, a_ptr, a_idx, b_ptr, b_idx, max_deg_a: int, max_deg_b: int, m: int, n: int):
+        self.pairs, self.a_ptr, self.a_idx, self.b_ptr, self.b_idx = pairs, a_ptr, a_idx, b_ptr, b_idx
+        self.max_deg_a, self.max_deg_b, self.m, self.n = int(max_deg_a), int(max_deg_b), int(m), int(n)
+        self.n_pairs = int(pairs.shape[0])
+
+
+def _pair_list_sites(name: str, x: torch.Tensor, c: torch.Tensor, tab: PairTables):
+    T, m, n = _pair_sites(name, x, c)
+    if (m, n) != (tab.m, tab.n) or tab.pairs.device != x.device:
+        raise ValueError(f"{name}: a pair list for ({tab.m}, {tab.n}) sites on {tab.pairs.device} with operands "
+                         f"{tuple(x.shape)}, {tuple(c.shape)} on {x.device}")
+    return T, m, n, tab.n_pairs
+
+
+def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int = PAIR_DIST,
+                   v: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(T, P) in the operands' dtype over u[t,p] = x[t,j_p] - c[t,i_p] (aggf_pair_list_dist): |u|, u.u or
+    (v[t,j_p] - y[t,i_p]).u by ``mode``, as ``pair_dist``."""
+    T, m, n, P = _pair_list_sites("pair_list_dist", x, c, tab)
+    if mode not in (PAIR_DIST, PAIR_SQDIST, PAIR_DOT):
+        raise ValueError(f"pair_list_dist: mode {mode}")
+    if mode == PAIR_DOT:
+        if v is None or y is None or (T, m, n) != _pair_sites("pair_list_dist", v, y) or v.dtype != x.dtype:
+            raise ValueError("pair_list_dist: PAIR_DOT needs v shaped as x and y shaped as c, in their dtype")
+    else:
+        v = y = None
+    out = torch.empty((T, P), dtype=x.dtype, device=x.device)
+    if out.numel() == 0:
+        return out
+    with _timed("pair_list_dist"):
+        check(lib().aggf_pair_list_dist(ptr(x), ptr(c), ptr(v), ptr(y), ptr(tab.pairs), T, m, n, P,
+                                        dtype_code(x.dtype), mode, ptr(out), stream_ptr()), "aggf_pair_list_dist")
+    return out
+
+
+def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairTables,
+                   dv: Optional[torch.Tensor] = None, want_a: bool = True, want_b: bool = True,
+                   out_dtype: Optional[torch.dtype] = None):
+    """(A, B): A[t,j,:] = sum_{p: j_p = j} w_p u_p (T, n, 3) and B[t,i,:] = -sum_{p: i_p = i} w_p u_p (T, m, 3) over
+    u[t,p] = x[t,j_p] - c[t,i_p], with the weights w (T, P) or, given ``dv``, (dv > 0 ? w / dv : 0)
+    (aggf_pair_list_pull).  An output that is not wanted is None and costs nothing.  All operands share a dtype at
+    least as wide as out_dtype (default: theirs)."""
+    T, m, n, P = _pair_list_sites("pair_list_pull", x, c, tab)
+    out_dtype = out_dtype or x.dtype
+    for name, arr in (("w", w), ("dv", dv)):
+        if arr is not None and (tuple(arr.shape) != (T, P) or arr.dtype != x.dtype or not arr.is_contiguous()):
+            raise ValueError(f"pair_list_pull: {name} {tuple(arr.shape)} {arr.dtype} for {P} pairs of sites "
+                             f"{tuple(x.shape)} {tuple(c.shape)} {x.dtype} (contiguous arrays of one dtype)")
+    if x.dtype == torch.float32 and out_dtype == torch.float64:
+        raise ValueError("pair_list_pull: float32 operands with float64 outputs: widen the operands")
+    a = torch.empty((T, n, 3), dtype=out_dtype, device=x.device) if want_a else None
+    b = torch.empty((T, m, 3), dtype=out_dtype, device=x.device) if want_b else None
+    if T * P == 0 or T * m * n == 0:  # empty sums
+        return (a.zero_() if want_a else None), (b.zero_() if want_b else None)
+    if not (want_a or want_b):
+        return None, None
+    with _timed("pair_list_pull"):
+        check(lib().aggf_pair_list_pull(ptr(w), ptr(dv), ptr(x), ptr(c), ptr(tab.pairs), ptr(tab.a_ptr),
+                                        ptr(tab.a_idx), ptr(tab.b_ptr), ptr(tab.b_idx), tab.max_deg_a, tab.max_deg_b,
+                                        T, m, n, P, dtype_code(x.dtype), ptr(a), ptr(b), dtype_code(out_dtype),
+                                        stream_ptr()), "aggf_pair_list_pull")
+    return a, b
+
+
 # ------------------------------------------------------------------ K10 Gaussian radial basis (aggforce_amd/_autograd.py)
 GB_H_ELEM, GB_H_ROW, GB_H_SLOT = 0, 1, 2
 

@@ -179,6 +179,26 @@ struct Vec16<float> {
   static constexpr int N = 4;
 };
 
+// ---- one element of a K9 pair array from the displacement d = X[t,j] - C[t,i] (and, in DOT mode, e = V[t,j] - Y[t,i]):
+// the one expression of the matrix kernel (K9a) and the pair-list kernel (K9c), so that the two agree bit for bit.
+// a0 b0 + a1 b1 + a2 b2 with its roundings written out: which products fuse into an FMA is otherwise the compiler's
+// choice per kernel (it packs two float products of K9a into one v_pk_mul_f32, and fuses all three where it cannot),
+// and two kernels that differ in it differ in the last bit.  These are the sequences K9a has had since it shipped.
+__device__ __forceinline__ float pair_dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(a1, b1, a0 * b0) + a2 * b2;
+}
+__device__ __forceinline__ double pair_dot3(double a0, double b0, double a1, double b1, double a2, double b2) {
+#pragma clang fp contract(off)
+  return __builtin_fma(a2, b2, __builtin_fma(a0, b0, a1 * b1));
+}
+template <typename T, int MODE>
+__device__ __forceinline__ T pair_element(T d0, T d1, T d2, T e0, T e1, T e2) {
+  if (MODE == AGGF_PAIR_DOT) return pair_dot3(e0, d0, e1, d1, e2, d2);
+  const T val = pair_dot3(d0, d0, d1, d1, d2, d2);
+  return MODE == AGGF_PAIR_DIST ? sqrt(val) : val;
+}
+
 // ---- Philox4x32-10 (Salmon et al., SC'11): counter = 64-bit quad index, key = seed ----
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;

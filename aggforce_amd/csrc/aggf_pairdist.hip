@@ -59,13 +59,7 @@ __global__ __launch_bounds__(256) void pairdist_kernel(const T* __restrict__ X, 
 #pragma unroll
       for (int k = 0; k < PD_K; ++k) {
         const T d0 = x[k][0] - c0, d1 = x[k][1] - c1, d2 = x[k][2] - c2;
-        T val;
-        if (MODE == AGGF_PAIR_DOT) {
-          val = (v[k][0] - y0) * d0 + (v[k][1] - y1) * d1 + (v[k][2] - y2) * d2;
-        } else {
-          val = d0 * d0 + d1 * d1 + d2 * d2;
-          if (MODE == AGGF_PAIR_DIST) val = sqrt(val);
-        }
+        const T val = pair_element<T, MODE>(d0, d1, d2, v[k][0] - y0, v[k][1] - y1, v[k][2] - y2);
         if (live[k]) o[64 * k] = val;
       }
     }

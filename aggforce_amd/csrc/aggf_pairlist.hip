@@ -1,0 +1,260 @@
+// K9c / K9d: pair distances over a static list of P pairs (i_p, j_p) shared by all frames
+// (aggforce_amd/_autograd.py: PairListDist, PairListPull, PairListDot; jaxutil.pair_distances, and the upper triangles
+// of jaxutil.distances, whose list is triu_indices).  With u[t,p] = X[t,j_p] - C[t,i_p] (X (T, n, 3), C (T, m, 3)):
+//
+//   pairlist_kernel<T, MODE>        out[t,p] = sqrt(u.u) | u.u | (V[t,j_p] - Y[t,i_p]).u   the (T, P) array written once
+//   pairlist_pull_kernel<.., FORM>  S[t,s,:] = sum_{p incident to s} w[t,p] (Own[t,s] - Oth[t,o_p]): with the table by j
+//                                   (Own = X, Oth = C) that is A[t,j,:] = sum w u, with the table by i (Own = C,
+//                                   Oth = X) it is B[t,i,:] = -sum w u (-(a - b) is b - a exactly); w = W or
+//                                   (Dv > 0 ? W / Dv : 0)
+//
+// The arrays of a call are T P elements where K9a / K9b move T m n.  No atomics: a site's sum walks its entries of the
+// incidence table (CSR: ptr, pair index, ascending pair index), so results are bit-identical run to run.  Element
+// offsets are 64-bit; base addresses need only element alignment.  Every index read from a table is tested against the
+// size of the array it addresses, so that no list a caller of the C ABI passes can make a kernel read outside X, C, W
+// or the tables: a pair with a bad site writes NaN (K9c) or adds nothing (K9d).
+#include "aggf_common.h"
+
+namespace aggf {
+
+// ---------------------------------------------------------------------------
+// K9c.  One wave = 64 consecutive pairs x a block of `frames` frames: a lane loads its pair's two indices once and
+// walks the frames, so a wave's store is 64 consecutive elements of a row of out whatever P is.  The two sites of an
+// element are gathered from the frame's rows of X and C (3 n and 3 m values: cache-resident).  Waves take the
+// (frame block, pair block) tasks in output order; `frames` is the launcher's choice (all frames unless that leaves
+// too few tasks).
+constexpr int PL_MIN_FRAMES = 8;
+constexpr int64_t PL_TARGET_TASKS = 16384;
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void pairlist_kernel(const T* __restrict__ X, const T* __restrict__ C,
+                                                       const T* __restrict__ V, const T* __restrict__ Y,
+                                                       const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
+                                                       int32_t n, int64_t P, int64_t frames, T* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t pblocks = (P + 63) / 64, fblocks = (nT + frames - 1) / frames;
+  const int64_t ntask = pblocks * fblocks;
+  for (int64_t task = (int64_t)blockIdx.x * 4 + wave; task < ntask; task += (int64_t)gridDim.x * 4) {
+    const int64_t fb = task / pblocks, pb = task - fb * pblocks;
+    const int64_t p = pb * 64 + lane;
+    if (p >= P) continue;
+    const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+    const int64_t t0 = fb * frames, t1 = t0 + frames < nT ? t0 + frames : nT;
+    T* o = out + t0 * P + p;
+    if (!((uint32_t)i < (uint32_t)m && (uint32_t)j < (uint32_t)n)) {
+      for (int64_t t = t0; t < t1; ++t, o += P) *o = (T)__builtin_nan("");
+      continue;
+    }
+    const int64_t xs = 3 * (int64_t)n, cs = 3 * (int64_t)m;
+    const int64_t xo = t0 * xs + 3 * (int64_t)j, co = t0 * cs + 3 * (int64_t)i;
+    const T* x = X + xo;
+    const T* c = C + co;
+    const T* v = MODE == AGGF_PAIR_DOT ? V + xo : nullptr;
+    const T* y = MODE == AGGF_PAIR_DOT ? Y + co : nullptr;
+#pragma unroll 4
+    for (int64_t t = t0; t < t1; ++t, x += xs, c += cs, o += P) {
+      const T d0 = x[0] - c[0], d1 = x[1] - c[1], d2 = x[2] - c[2];
+      T e0 = 0, e1 = 0, e2 = 0;
+      if (MODE == AGGF_PAIR_DOT) {
+        e0 = v[0] - y[0], e1 = v[1] - y[1], e2 = v[2] - y[2];
+        v += xs, y += cs;
+      }
+      *o = pair_element<T, MODE>(d0, d1, d2, e0, e1, e2);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// K9d.  One launch per output: the sums of the sites of one incidence table.  Entry e of site s is the pair p = idx[e],
+// ptr[s] <= e < ptr[s + 1], and the pair's other site is column `ocol` of `pairs`.  Every term is formed in the input
+// dtype (as K9b forms it) and every sum is accumulated in float64 throughout, then narrowed once.
+//   FORM 0, a lane per (frame, site): the lane walks its entries in ascending pair index.  Bonded lists, a few entries
+//           per site; consecutive lanes are consecutive sites of one frame.
+//   FORM 1, a wave per (frame, site): lane l takes entries l, l + 64, ... in ascending order, a fixed xor butterfly
+//           adds the 64 lane sums.  The triangle, where a site has n - 1 entries, and any list with a long run.
+// A site without entries gets zeros.  The launcher takes FORM 1 when the table's longest run exceeds PLP_LANE_DEG.
+// PLP_LANE_DEG = 32 is NOT MEASURED yet: it is half a wave's lanes, the run at which a wave per site keeps at least
+// half its lanes busy.  `tools/distgrad_bench.py --pairlist` times both forms on lists of 2 .. 128 entries per site
+// (its form_sweep rows); the crossing it finds belongs here with the figure.
+constexpr int PLP_LANE = 0, PLP_WAVE = 1;
+constexpr int32_t PLP_LANE_DEG = 32;
+
+template <typename TI, bool HAS_DV>
+__device__ __forceinline__ TI pull_weight(const TI* __restrict__ W, const TI* __restrict__ Dv, int64_t e) {
+  TI wv = W[e];
+  if (HAS_DV) {
+    const TI dv = Dv[e];
+    const TI qv = wv / dv;  // (formed before the choice, as in K9b)
+    wv = dv > (TI)0 ? qv : (TI)0;
+  }
+  return wv;
+}
+
+template <typename TI, typename TO, bool HAS_DV, int FORM>
+__global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict__ W, const TI* __restrict__ Dv,
+                                                            const TI* __restrict__ Own, const TI* __restrict__ Oth,
+                                                            const int32_t* __restrict__ pairs, int32_t ocol,
+                                                            const int32_t* __restrict__ ptr,
+                                                            const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
+                                                            int32_t no, int64_t P, TO* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ntask = nT * ns;
+  const int64_t first = FORM == PLP_LANE ? (int64_t)blockIdx.x * 256 + threadIdx.x
+                                         : (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t step = (int64_t)gridDim.x * (FORM == PLP_LANE ? 256 : 4);
+  for (int64_t task = first; task < ntask; task += step) {
+    const int64_t t = task / ns, s = task - t * ns;
+    const TI* own = Own + task * 3;
+    const TI o0 = own[0], o1 = own[1], o2 = own[2];
+    const TI* oth = Oth + t * no * 3;
+    const TI* w = W + t * P;
+    const TI* dv = HAS_DV ? Dv + t * P : nullptr;
+    int64_t beg = ptr[s], end = ptr[s + 1];  // (a run is clipped to the P entries the table has)
+    beg = beg < 0 ? 0 : beg;
+    end = end > P ? P : end;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int64_t e = FORM == PLP_LANE ? beg : beg + lane; e < end; e += FORM == PLP_LANE ? 1 : 64) {
+      const int32_t p = idx[e];
+      if (!((uint32_t)p < (uint64_t)P)) continue;
+      const int32_t o = pairs[2 * (int64_t)p + ocol];
+      if (!((uint32_t)o < (uint32_t)no)) continue;
+      const TI wv = pull_weight<TI, HAS_DV>(w, dv, p);
+      const TI* r = oth + 3 * (int64_t)o;
+      a0 += (double)(wv * (o0 - r[0])), a1 += (double)(wv * (o1 - r[1])), a2 += (double)(wv * (o2 - r[2]));
+    }
+    if (FORM == PLP_WAVE) {
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        a0 += __shfl_xor(a0, d, 64), a1 += __shfl_xor(a1, d, 64), a2 += __shfl_xor(a2, d, 64);
+      }
+    }
+    if (FORM == PLP_LANE || lane == 0) {
+      TO* dst = out + task * 3;
+      dst[0] = (TO)a0, dst[1] = (TO)a1, dst[2] = (TO)a2;
+    }
+  }
+}
+
+static inline dim3 pairlist_grid(int64_t blocks) {
+  if (blocks > 65536) blocks = 65536;
+  if (blocks < 1) blocks = 1;
+  return dim3((unsigned)blocks);
+}
+
+// the sizes of one call: T P and 3 T max(m, n) as element counts that fit a 64-bit byte offset, P within int32
+static int pairlist_shape(const char* who, int64_t T, int32_t m, int32_t n, int64_t P, int64_t* count) {
+  if (T < 0 || m < 0 || n < 0 || P < 0) return fail(AGGF_ERR_ARG, "%s: negative shape", who);
+  if (P > INT32_MAX) return fail(AGGF_ERR_ARG, "%s: more than 2^31 - 1 pairs", who);
+  int64_t sites = 0;
+  if (__builtin_mul_overflow(T, P, count) || *count > INT64_MAX / 8)
+    return fail(AGGF_ERR_ARG, "%s: T P does not fit a 64-bit byte offset", who);
+  if (__builtin_mul_overflow(T, 3 * (int64_t)(m > n ? m : n), &sites) || sites > INT64_MAX / 8)
+    return fail(AGGF_ERR_ARG, "%s: T n does not fit a 64-bit byte offset", who);
+  return AGGF_OK;
+}
+
+template <typename T>
+static void launch_pairlist(int mode, dim3 grid, hipStream_t stream, const void* X, const void* C, const void* V,
+                            const void* Y, const int32_t* pairs, int64_t nT, int32_t m, int32_t n, int64_t P,
+                            int64_t frames, void* out) {
+  const dim3 block(256);
+  if (mode == AGGF_PAIR_DIST)
+    AGGF_LAUNCH((pairlist_kernel<T, AGGF_PAIR_DIST>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,
+                (const T*)Y, pairs, nT, m, n, P, frames, (T*)out);
+  else if (mode == AGGF_PAIR_SQDIST)
+    AGGF_LAUNCH((pairlist_kernel<T, AGGF_PAIR_SQDIST>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,
+                (const T*)Y, pairs, nT, m, n, P, frames, (T*)out);
+  else
+    AGGF_LAUNCH((pairlist_kernel<T, AGGF_PAIR_DOT>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,
+                (const T*)Y, pairs, nT, m, n, P, frames, (T*)out);
+}
+
+template <typename TI, typename TO, bool HAS_DV>
+static void launch_pull_form(int form, hipStream_t stream, const void* W, const void* Dv, const void* Own,
+                             const void* Oth, const int32_t* pairs, int32_t ocol, const int32_t* ptr,
+                             const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, void* out) {
+  const dim3 block(256);
+  const int64_t tasks = nT * ns;
+  if (form == PLP_LANE)
+    AGGF_LAUNCH((pairlist_pull_kernel<TI, TO, HAS_DV, PLP_LANE>), pairlist_grid(ceil_div(tasks, 256)), block, 0, stream,
+                (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no, P,
+                (TO*)out);
+  else
+    AGGF_LAUNCH((pairlist_pull_kernel<TI, TO, HAS_DV, PLP_WAVE>), pairlist_grid(ceil_div(tasks, 4)), block, 0, stream,
+                (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no, P,
+                (TO*)out);
+}
+
+// the sums of one table (nothing to do without sites)
+static void launch_pull(int in_dtype, int out_dtype, int32_t max_deg, hipStream_t stream, const void* W, const void* Dv,
+                        const void* Own, const void* Oth, const int32_t* pairs, int32_t ocol, const int32_t* ptr,
+                        const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, void* out) {
+  if (ns == 0) return;
+  const int form = max_deg > PLP_LANE_DEG ? PLP_WAVE : PLP_LANE;
+#define AGGF_PULL_FORM(TI, TO)                                                                                       \
+  (Dv ? launch_pull_form<TI, TO, true>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, out)     \
+      : launch_pull_form<TI, TO, false>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, out))
+  if (in_dtype == AGGF_F32)
+    AGGF_PULL_FORM(float, float);
+  else if (out_dtype == AGGF_F32)
+    AGGF_PULL_FORM(double, float);
+  else
+    AGGF_PULL_FORM(double, double);
+#undef AGGF_PULL_FORM
+}
+
+}  // namespace aggf
+
+using namespace aggf;
+
+extern "C" int aggf_pair_list_dist(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
+                                   int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, void* out,
+                                   void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  int64_t count = 0;
+  const int rc = pairlist_shape("aggf_pair_list_dist", T, m, n, P, &count);
+  if (rc != AGGF_OK) return rc;
+  if (dtype != AGGF_F32 && dtype != AGGF_F64) return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: bad dtype");
+  if (mode != AGGF_PAIR_DIST && mode != AGGF_PAIR_SQDIST && mode != AGGF_PAIR_DOT)
+    return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: bad mode");
+  if (count == 0) return AGGF_OK;
+  if (!X || !C || !pairs || !out) return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: NULL pointer");
+  if (mode == AGGF_PAIR_DOT && (!V || !Y)) return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: DOT needs V and Y");
+  // a wave walks all frames of its 64 pairs unless that leaves the chip short of tasks
+  const int64_t pblocks = ceil_div(P, 64);
+  int64_t frames = T;
+  while (frames > PL_MIN_FRAMES && pblocks * ceil_div(T, frames) < PL_TARGET_TASKS) frames = (frames + 1) / 2;
+  const int64_t waves = pblocks * ceil_div(T, frames);  // <= count
+  const dim3 grid = pairlist_grid(ceil_div(waves, 4));
+  if (dtype == AGGF_F64)
+    launch_pairlist<double>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, out);
+  else
+    launch_pairlist<float>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, out);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+extern "C" int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void* C, const int32_t* pairs,
+                                   const int32_t* a_ptr, const int32_t* a_idx, const int32_t* b_ptr,
+                                   const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m,
+                                   int32_t n, int64_t P, int in_dtype, void* A, void* B, int out_dtype,
+                                   void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  int64_t count = 0;
+  const int rc = pairlist_shape("aggf_pair_list_pull", T, m, n, P, &count);
+  if (rc != AGGF_OK) return rc;
+  if ((in_dtype != AGGF_F32 && in_dtype != AGGF_F64) || (out_dtype != AGGF_F32 && out_dtype != AGGF_F64))
+    return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: bad dtype");
+  if (in_dtype == AGGF_F32 && out_dtype == AGGF_F64)
+    return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: float32 inputs with float64 outputs: widen the inputs");
+  if (max_deg_a < 0 || max_deg_b < 0) return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: negative degree");
+  if (count == 0 || (!A && !B)) return AGGF_OK;
+  if (!W || !X || !C || !pairs) return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: NULL pointer");
+  if ((A && (!a_ptr || !a_idx)) || (B && (!b_ptr || !b_idx)))
+    return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: an output without its incidence table");
+  if (A) launch_pull(in_dtype, out_dtype, max_deg_a, stream, W, Dv, X, C, pairs, 0, a_ptr, a_idx, T, n, m, P, A);
+  if (B) launch_pull(in_dtype, out_dtype, max_deg_b, stream, W, Dv, C, X, pairs, 1, b_ptr, b_idx, T, m, n, P, B);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}

@@ -320,6 +320,50 @@ int main() {
                                     sel & 2 ? d + 4096 : nullptr, od, ws, wpl, nullptr));
         }
       }
+  // K9c / K9d: refusals (NULL pointers, bad dtype / mode, negative or oversized shapes, an output without its table),
+  // empty problems (no launch, no pointer needed), and plausible calls in every mode / dtype pair / output selection /
+  // form of the pull kernel (the degrees on either side of its threshold)
+  REFUSED(aggf_pair_list_dist(nullptr, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, d, nullptr));
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, nullptr, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, d, nullptr));  // no list
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, nullptr, nullptr));
+  REFUSED(aggf_pair_list_dist(p, p, p, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DOT, d, nullptr));            // DOT without Y
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 2, AGGF_PAIR_DIST, d, nullptr));     // dtype
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, 3, d, nullptr));                  // mode
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, -1, 3, 5, 9, 1, AGGF_PAIR_DIST, d, nullptr));
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, 7, 3, 5, -9, 1, AGGF_PAIR_DIST, d, nullptr));
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, 7, 3, 5, (int64_t)1 << 31, 1, AGGF_PAIR_DIST, d, nullptr));  // P
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, (int64_t)1 << 40, 3, 5, 1 << 30, 1, AGGF_PAIR_DIST, d, nullptr));  // T P
+  REFUSED(aggf_pair_list_dist(p, p, nullptr, nullptr, i32, INT64_MAX / 4, 3, 5, 1, 1, AGGF_PAIR_DIST, d, nullptr));     // T n
+  RUNS(aggf_pair_list_dist(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 3, 5, 9, 1, AGGF_PAIR_DIST, nullptr, nullptr));
+  RUNS(aggf_pair_list_dist(nullptr, nullptr, nullptr, nullptr, nullptr, 7, 3, 5, 0, 0, AGGF_PAIR_DOT, nullptr, nullptr));
+  REFUSED(aggf_pair_list_pull(nullptr, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, nullptr, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, nullptr, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, d, d, 1, nullptr));  // no list
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, nullptr, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, d, d, 1, nullptr));  // A, no table
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, nullptr, 2, 2, 7, 3, 5, 9, 1, d, d, 1, nullptr));  // B, no table
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 0, d, d, 1, nullptr));  // float32 in, float64 out
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, d, d, 5, nullptr));
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, -3, 5, 9, 1, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, -1, 2, 7, 3, 5, 9, 1, d, d, 1, nullptr));  // degree
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, (int64_t)1 << 31, 1, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, INT64_MAX / 4, 3, 5, 9, 1, d, d, 1, nullptr));
+  RUNS(aggf_pair_list_pull(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 7, 3, 5, 0, 1, nullptr, nullptr, 1, nullptr));
+  RUNS(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, nullptr, nullptr, 1, nullptr));  // neither output
+  RUNS(aggf_pair_list_pull(p, nullptr, p, p, i32, i32, i32, nullptr, nullptr, 2, 2, 7, 3, 5, 9, 1, d, nullptr, 1, nullptr));  // A alone
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)100000})
+    for (int32_t m : {1, 17, 257})
+      for (int32_t n : {1, 65, 8200})
+        for (int64_t P : {(int64_t)1, (int64_t)65, (int64_t)32640})
+          for (int in = 0; in < 2; ++in) {
+            for (int mode : {AGGF_PAIR_DIST, AGGF_PAIR_SQDIST, AGGF_PAIR_DOT})
+              RUNS(aggf_pair_list_dist(p, (char*)p + 4096, p, (char*)p + 4096, i32, T, m, n, P, in, mode, d, nullptr));
+            for (int od = 0; od <= in; ++od)
+              for (int sel = 1; sel < 4; ++sel)
+                for (int32_t deg : {0, 2, 32, 33, 8199})
+                  RUNS(aggf_pair_list_pull(p, sel == 3 ? p : nullptr, p, (char*)p + 4096, i32, i32, i32, i32, i32, deg,
+                                           8199 - deg, T, m, n, P, in, sel & 1 ? d : nullptr,
+                                           sel & 2 ? d + 4096 : nullptr, od, nullptr));
+          }
   // K10: the partials' size over the grid of shapes (absurd ones give 0), refusals (NULL pointers, bad dtype / width /
   // clip / order / form, rows or outputs that do not fit, slot tables that do not match the form, short or misaligned
   // workspaces), empty shapes, and plausible calls in every dtype / form / slot selection with the queried workspace

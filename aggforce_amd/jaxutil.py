@@ -7,6 +7,11 @@ no (T, m, n, 3) displacement array is formed, forward or backward, and a zero di
 matrix, coincident sites) has gradient 0 at every order -- plain torch returns NaN from the second order on.  Its
 other forms (``return_displacements``, CPU tensors, NumPy inputs, other dtypes) and ``abatch`` are plain torch code:
 autograd handles them.
+
+``pair_distances`` is the same over a static list of pairs (``PairList``: bonded pairs, non-bonded pairs with
+exclusions, site-to-atom lists) on K9c / K9d through ``PairListDist`` / ``PairListPull`` / ``PairListDot``: every array
+is (T, n_pairs), forward and backward.  The upper triangles of ``distances(x, return_matrix=False)`` are the list
+``PairList.upper_triangle(n)``, so they never form the (T, n, n) matrix.
 """
 from typing import Callable, Union
 
@@ -97,6 +102,135 @@ def _upper_triangles(dist: torch.Tensor) -> torch.Tensor:
     return dist[:, i0, i1]
 
 
+def _incidence(sites: np.ndarray, n: int):
+    """CSR table of the pairs at each of ``n`` sites: (ptr (n + 1,), pair index (P,)) int32, a site's pairs in
+    ascending pair index (a stable sort of the pairs by site), and the longest run."""
+    idx = np.argsort(sites, kind="stable").astype(np.int32)
+    counts = np.bincount(sites, minlength=n) if sites.size else np.zeros(n, dtype=np.int64)
+    ptr = np.zeros(n + 1, dtype=np.int32)
+    np.cumsum(counts, out=ptr[1:])
+    return ptr, idx, int(counts.max()) if n else 0
+
+
+class PairList:
+    """A static list of site pairs shared by all frames, validated on the host once: ``pairs`` (P, 2) integers (a
+    list, a NumPy array or a torch tensor on any device), row p = (i_p, j_p) with ``0 <= j_p < n_sites`` and
+    ``0 <= i_p < n_cross`` (``n_cross`` None: the self form, both sites among the same ``n_sites``).  The order
+    (i, j) = (other, self) is that of the (T, other, self) result of ``distances``.  Repeated pairs are allowed (each
+    is its own column), so are i == j in the self form (distance 0, gradient weight 0) and an empty list.
+
+    The device side -- the int32 index array and the two incidence tables (the pairs of every j and of every i, in
+    ascending pair index) that the backward kernel sums over -- is built on first use, once per device."""
+
+    _triangles: dict = {}
+
+    def __init__(self, pairs, n_sites: int, n_cross: Union[int, None] = None):
+        if isinstance(pairs, torch.Tensor):
+            if pairs.dtype.is_floating_point or pairs.dtype.is_complex or pairs.dtype == torch.bool:
+                raise ValueError(f"pairs must be integers; got {pairs.dtype}")
+            arr = pairs.detach().cpu().numpy()
+        else:
+            arr = np.asarray(pairs)
+            if arr.size == 0 and arr.dtype.kind == "f":  # ([] and [[]] come out as float64)
+                arr = arr.astype(np.int64)
+        if arr.dtype.kind not in "iu":
+            raise ValueError(f"pairs must be integers; got {arr.dtype}")
+        if arr.ndim == 1 and arr.size == 0:
+            arr = arr.reshape(0, 2)
+        if arr.ndim != 2 or arr.shape[1] != 2:
+            raise ValueError(f"pairs must have shape (n_pairs, 2); got {arr.shape}")
+        if arr.dtype == np.uint64 and arr.size and int(arr.max()) > np.iinfo(np.int64).max:
+            raise ValueError("pairs holds an index beyond the int64 range")
+        self.n_sites = int(n_sites)
+        self.n_cross = None if n_cross is None else int(n_cross)
+        if self.n_sites < 0 or (self.n_cross is not None and self.n_cross < 0):
+            raise ValueError(f"negative number of sites: n_sites {n_sites}, n_cross {n_cross}")
+        self.pairs = np.array(arr, dtype=np.int64)  # (a copy: the list is a constant from here on)
+        self.pairs.setflags(write=False)
+        self.n_pairs = int(self.pairs.shape[0])
+        m = self.n_rows
+        if max(m, self.n_sites, self.n_pairs) > np.iinfo(np.int32).max:
+            raise ValueError("a pair list is limited to 2^31 - 1 pairs and sites")
+        bad = (self.pairs[:, 0] < 0) | (self.pairs[:, 0] >= m) | (self.pairs[:, 1] < 0) | (self.pairs[:, 1] >= self.n_sites)
+        if bad.any():
+            row = int(np.argmax(bad))
+            raise ValueError(f"pairs row {row} = ({self.pairs[row, 0]}, {self.pairs[row, 1]}) is out of range: "
+                             f"i must be in [0, {m}) and j in [0, {self.n_sites})")
+        self._host = None
+        self._devices: dict = {}
+
+    @property
+    def n_rows(self) -> int:
+        """The number of sites i runs over: ``n_cross``, or ``n_sites`` in the self form."""
+        return self.n_sites if self.n_cross is None else self.n_cross
+
+    @classmethod
+    def upper_triangle(cls, n_sites: int) -> "PairList":
+        """The pairs i < j of ``n_sites`` sites in the order of ``torch.triu_indices(n, n, offset=1)`` (what
+        ``distances(x, return_matrix=False)`` returns); one object per ``n_sites``, kept."""
+        n_sites = int(n_sites)
+        if n_sites not in cls._triangles:
+            if len(cls._triangles) >= 8:  # (a handful of system sizes per process; the tables are O(n^2))
+                cls._triangles.pop(next(iter(cls._triangles)))
+            cls._triangles[n_sites] = cls(np.stack(np.triu_indices(n_sites, k=1), axis=1), n_sites)
+        return cls._triangles[n_sites]
+
+    def tables(self):
+        """The incidence tables on the host: ``(by_j, by_i)``, each ``(ptr, pair index, longest run)``."""
+        if self._host is None:
+            self._host = (_incidence(self.pairs[:, 1], self.n_sites), _incidence(self.pairs[:, 0], self.n_rows))
+        return self._host
+
+    def on(self, device) -> "K.PairTables":
+        """The list on ``device`` (cached): see ``_kernels.PairTables``."""
+        device = torch.device(device)
+        if device not in self._devices:
+            (a_ptr, a_idx, a_deg), (b_ptr, b_idx, b_deg) = self.tables()
+            put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            self._devices[device] = K.PairTables(put(self.pairs.astype(np.int32)), put(a_ptr), put(a_idx), put(b_ptr),
+                                                 put(b_idx), a_deg, b_deg, self.n_rows, self.n_sites)
+        return self._devices[device]
+
+
+def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False) -> torch.Tensor:
+    """Differentiable distances over a list of pairs: (n_steps, n_pairs),
+    ``out[t, p] = |xyz[t, j_p] - (cross_xyz if given else xyz)[t, i_p]|`` (squared with ``square``), for ``pairs`` a
+    ``PairList`` or any (n_pairs, 2) integer array of rows (i_p, j_p) -- the index order of the (T, other, self) result
+    of ``distances``: with the pairs of ``torch.triu_indices`` this is ``distances(xyz)[:, i, j]``.
+
+    float32/float64 GPU tensors run on the K9c / K9d kernels (``PairListDist``): nothing of the size of the distance
+    matrix is formed, forward or backward, the result is differentiable in both arrays to any order, and a zero
+    distance has gradient 0.  CPU tensors, NumPy inputs and other dtypes take plain torch operations."""
+    def shape_of(a):
+        return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+    shapes = [shape_of(xyz)] + ([] if cross_xyz is None else [shape_of(cross_xyz)])
+    for s in shapes:
+        if len(s) != 3 or s[2] != 3:
+            raise ValueError(f"sites must have shape (n_steps, n_sites, 3); got {s}")
+    if len(shapes) == 2 and shapes[0][0] != shapes[1][0]:
+        raise ValueError(f"xyz {shapes[0]} and cross_xyz {shapes[1]} differ in their number of frames")
+    n_sites, n_cross = shapes[0][1], (None if cross_xyz is None else shapes[1][1])
+    plist = pairs if isinstance(pairs, PairList) else PairList(pairs, n_sites, n_cross)
+    if (plist.n_sites, plist.n_cross) != (n_sites, n_cross):
+        raise ValueError(f"a pair list for n_sites {plist.n_sites}, n_cross {plist.n_cross} with xyz {shapes[0]}"
+                         + ("" if cross_xyz is None else f" and cross_xyz {shapes[1]}"))
+    if _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
+        from ._autograd import PairListDist
+
+        K.lib()
+        return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square))
+    xyz = xyz if isinstance(xyz, torch.Tensor) else torch.as_tensor(np.asarray(xyz))
+    if cross_xyz is None:
+        other = xyz
+    else:
+        other = cross_xyz if isinstance(cross_xyz, torch.Tensor) else torch.as_tensor(np.asarray(cross_xyz))
+    i = torch.from_numpy(plist.pairs[:, 0].copy()).to(other.device)
+    j = torch.from_numpy(plist.pairs[:, 1].copy()).to(xyz.device)
+    disp = xyz[:, j] - other[:, i]
+    return (disp**2).sum(dim=-1) if square else torch.linalg.vector_norm(disp, dim=-1)
+
+
 def distances(
     xyz: torch.Tensor,
     cross_xyz: Union[torch.Tensor, None] = None,
@@ -112,11 +246,12 @@ def distances(
     if return_displacements and not return_matrix:
         raise ValueError("Displacements only supported when return_matrix is truthy.")
     if not return_displacements and _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
+        if not return_matrix:  # the pairs i < j as a list: no (T, n, n) array, forward or backward
+            return pair_distances(xyz, PairList.upper_triangle(xyz.shape[1]), square=square)
         from ._autograd import PairDist
 
         K.lib()
-        dist = PairDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, bool(square))
-        return dist if return_matrix else _upper_triangles(dist)
+        return PairDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, bool(square))
     xyz = xyz if isinstance(xyz, torch.Tensor) else torch.as_tensor(np.asarray(xyz))
     if cross_xyz is None:
         disp = xyz[:, None, :, :] - xyz[:, :, None, :]

@@ -478,6 +478,42 @@ int aggf_pair_pull(const void* W, const void* Dv, const void* X, const void* C, 
                    void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K9c / K9d  The same three operations over a static list of P pairs shared by all frames
+ * (jaxutil.pair_distances and the upper triangles of jaxutil.distances; the autograd Functions
+ * PairListDist / PairListPull / PairListDot).  `pairs` (P, 2) int32 on the device, row p =
+ * (i_p, j_p) with 0 <= i_p < m and 0 <= j_p < n,
+ *     u[t,p] = X[t,j_p] - C[t,i_p]
+ * Pair arrays are (T, P): nothing of size T m n exists.  Repeated pairs and i_p == j_p are
+ * allowed.  dtype rules, alignment and 64-bit offsets as K9; P < 2^31.
+ *
+ * aggf_pair_list_dist (K9c): out[t,p] by `mode` (AGGF_PAIR_DIST / SQDIST / DOT with V, Y), the
+ *   same arithmetic per element as aggf_pair_dist: for the same sites the same bits.
+ * aggf_pair_list_pull (K9d):
+ *     A[t,j,:] =  sum_{p: j_p = j} w[t,p] u[t,p]      (T, n, 3)
+ *     B[t,i,:] = -sum_{p: i_p = i} w[t,p] u[t,p]      (T, m, 3)
+ *   w = W (T, P) if Dv == NULL, else (Dv > 0 ? W / Dv : 0).  A or B may be NULL.  Each output
+ *   needs its incidence table in CSR form: a_ptr (n + 1) and a_idx (P) list, for every j, the
+ *   pairs with j_p = j in ascending p (a_ptr[j] <= e < a_ptr[j + 1], p = a_idx[e]); b_ptr
+ *   (m + 1) / b_idx (P) the same by i_p.  max_deg_a / max_deg_b: the longest run of each table;
+ *   they only choose between the kernel's two forms (a lane or a wave per site).  Terms are
+ *   formed in in_dtype, every sum is accumulated in float64 in ascending pair order (the wave
+ *   form: per lane, then a fixed butterfly), without atomics: bit-identical run to run, and an
+ *   output computed alone has the bits it has beside the other.  A site without pairs gets 0.
+ *   One launch per output; no workspace.
+ * Both kernels test every index they read from `pairs` and the tables against the array it
+ * addresses: a pair with a site out of range gives NaN (dist) or adds nothing (pull) instead
+ * of reading outside X, C, W or the tables.  T or P zero returns AGGF_OK without a launch and
+ * without writing (the sums of an empty list are the caller's zeros).
+ * ------------------------------------------------------------------------- */
+int aggf_pair_list_dist(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
+                        int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, void* out,
+                        void* stream);
+int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void* C, const int32_t* pairs,
+                        const int32_t* a_ptr, const int32_t* a_idx, const int32_t* b_ptr,
+                        const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m,
+                        int32_t n, int64_t P, int in_dtype, void* A, void* B, int out_dtype, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K10  The clipped Gaussian radial basis of qp/jaxfeat.py and its derivatives of any order
  * (the autograd Functions Basis / BasisDot of aggforce_amd/_autograd.py; reference
  * jaxfeat.py:187-567, which JAX differentiates itself).  With z = (r - c_k) / width and

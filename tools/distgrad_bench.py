@@ -11,7 +11,16 @@ Prints one JSON line per case, (T, m, n) = (1e4, 256, 256) and (1e5, 64, 64) in 
              ``plain`` = the torch body restated below (displacements (T, m, n, 3), then a norm).  Device events, median
              of --reps, the two alternating in one loop; ``*_peak_gb`` = torch.cuda.max_memory_allocated of one step.
              The plain double backward returns NaN (the zero diagonal); its time and memory are still those of the ops.
+With --pairlist the rows of the pair-list kernels instead (K9c / K9d, device events, median of --reps):
+  triangle_*   the list triu_indices at the four cases: list_dist / list_dot (K9c), list_pull / list_pull_dv (K9d),
+               with ``matrix_*`` = K9a / K9b on the (T, n, n) matrix of the same sites in the same run; and the upper
+               triangles end to end, U = sum exp(-(d - 1)^2) over i < j: ``list`` = jaxutil.distances(x,
+               return_matrix=False), ``matrix`` = the route of the commit --parent (the matrix, then a gather) rebuilt
+               in the same process, the two alternating; ``*_matrix_ms_min_max`` = the spread of the matrix route's repeats
+  bonded_*     a 256-site chain with its 1-3 and 1-4 neighbours (762 pairs), 1e4 frames
+  form_sweep_* K9d's lane-per-site and wave-per-site forms on lists of 2 .. 128 entries per site (PLP_LANE_DEG)
 Usage (GPU box): python tools/distgrad_bench.py [--rocprof OUTDIR] > profiles/distgrad_bench.jsonl
+                 python tools/distgrad_bench.py --pairlist --parent HASH >> profiles/distgrad_bench.jsonl
 """
 import argparse
 import csv
@@ -134,6 +143,151 @@ def end_to_end(x, reps):
     return out
 
 
+# ------------------------------------------------------------------ pair lists (K9c / K9d): --pairlist
+def bonded_list(n):
+    """A chain with its 1-3 and 1-4 neighbours: (i, i + k), k = 1, 2, 3 (up to 3 entries per site and table)."""
+    import numpy as np
+
+    return np.concatenate([np.stack([np.arange(n - k), np.arange(k, n)], axis=1) for k in (1, 2, 3)])
+
+
+def ring_list(n, deg):
+    """Every site with its next ``deg`` sites around a ring: ``deg`` entries per site in both tables."""
+    import numpy as np
+
+    s = np.arange(n)
+    return np.concatenate([np.stack([s, (s + k) % n], axis=1) for k in range(1, deg + 1)])
+
+
+def median_ms(fn, reps):
+    fn()
+    return round(statistics.median(event_ms(fn) for _ in range(reps)), 4)
+
+
+def list_kernel_row(name, kind, pairs, T, n, dt, reps, matrix=True):
+    """K9c / K9d on one list, beside K9a / K9b on the (T, n, n) matrix of the same sites in the same run."""
+    import torch
+
+    from aggforce_amd import _kernels as K
+    from aggforce_amd.jaxutil import PairList
+
+    s = 4 if dt == "f32" else 8
+    x, v, _ = make(T, 1, n, dt)
+    pl = PairList(pairs, n)
+    tab, P = pl.on("cuda"), pl.n_pairs
+    w = torch.randn((T, P), device="cuda", dtype=x.dtype)
+    d = K.pair_list_dist(x, x, tab)
+    rec = {"case": name, "list": kind, "T": T, "n": n, "P": P, "dtype": dt, "timing": "events",
+           "max_degree": [pl.tables()[0][2], pl.tables()[1][2]]}
+    calls = {"list_dist": lambda: K.pair_list_dist(x, x, tab), "list_dot": lambda: K.pair_list_dist(x, x, tab, K.PAIR_DOT, v, v),
+             "list_pull": lambda: K.pair_list_pull(w, x, x, tab), "list_pull_dv": lambda: K.pair_list_pull(w, x, x, tab, dv=d)}
+    sites = 3 * 2 * n
+    amount = {"list_dist": s * T * (P + sites), "list_dot": s * T * (P + 2 * sites), "list_pull": s * T * (P + 2 * sites),
+              "list_pull_dv": s * T * (2 * P + 2 * sites)}
+    for op, fn in calls.items():
+        rec[op + "_ms"] = median_ms(fn, reps)
+        rec[op + "_bytes"] = float(amount[op])
+        rec[op + "_tbps"] = round(amount[op] / (rec[op + "_ms"] * 1e-3) * 1e-12, 3)
+    del w, d, calls
+    torch.cuda.empty_cache()
+    if matrix:
+        wm = torch.randn((T, n, n), device="cuda", dtype=x.dtype)
+        for op, fn in op_calls(x, v, wm).items():
+            rec["matrix_" + op + "_ms"] = median_ms(fn, reps)
+            rec["matrix_" + op + "_tbps"] = round(op_bytes(op, T, n, n, s) / (rec["matrix_" + op + "_ms"] * 1e-3) * 1e-12, 3)
+        del wm
+    torch.cuda.empty_cache()
+    return rec, x
+
+
+def triangle_end_to_end(x, reps, parent):
+    """fwd_bwd and double_bwd of the upper triangles: ``list`` = jaxutil.distances(x, return_matrix=False) as it is,
+    ``matrix`` = the route of commit ``parent`` rebuilt from its pieces (the (T, n, n) matrix on K9a, then a gather),
+    alternating in one loop; the spread of the matrix route's own repeats is kept beside the medians."""
+    import torch
+
+    from aggforce_amd import jaxutil
+    from aggforce_amd._autograd import PairDist
+
+    def matrix_route(p):
+        return jaxutil._upper_triangles(PairDist.apply(p, p, False))
+
+    def list_route(p):
+        return jaxutil.distances(p, return_matrix=False)
+
+    def fwd_bwd(dist):
+        p = x.detach().requires_grad_(True)
+        torch.exp(-(dist(p) - 1) ** 2).sum().backward()
+        return p.grad
+
+    def double_bwd(dist):
+        p = x.detach().requires_grad_(True)
+        (g,) = torch.autograd.grad(torch.exp(-(dist(p) - 1) ** 2).sum(), p, create_graph=True)
+        return torch.autograd.grad((g * g).sum(), p)[0]
+
+    out = {"parent": parent, "parent_route": "rebuilt in this process: _upper_triangles(PairDist.apply(x, x))"}
+    paths = (("list", list_route), ("matrix", matrix_route))
+    for qname, quantity in (("fwd_bwd", fwd_bwd), ("double_bwd", double_bwd)):
+        times = {p: [] for p, _ in paths}
+        for rep in range(reps + 1):  # (the first round warms up)
+            for pname, dist in paths:
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                ms = event_ms(lambda: quantity(dist))
+                out[f"{qname}_{pname}_peak_gb"] = round(torch.cuda.max_memory_allocated() / 1e9, 3)
+                if rep:
+                    times[pname].append(ms)
+        for pname, ts in times.items():
+            out[f"{qname}_{pname}_ms"] = round(statistics.median(ts), 3)
+        out[f"{qname}_matrix_ms_min_max"] = [round(min(times["matrix"]), 3), round(max(times["matrix"]), 3)]
+        out[f"{qname}_matrix_over_list"] = round(out[f"{qname}_matrix_ms"] / out[f"{qname}_list_ms"], 2)
+    out["double_bwd_list_finite"] = bool(torch.isfinite(double_bwd(list_route)).all())
+    return out
+
+
+def form_sweep(T, n, dt, reps):
+    """K9d's two forms on ring lists of growing degree, the form forced through the degree handed to the C entry
+    point (which only chooses the form): where the wave per site overtakes the lane per site."""
+    import torch
+
+    from aggforce_amd import _kernels as K
+    from aggforce_amd.jaxutil import PairList
+
+    x, _, _ = make(T, 1, n, dt)
+    rec = {"case": f"form_sweep_n{n}_{dt}", "T": T, "n": n, "dtype": dt, "timing": "events", "degree": [], "lane_ms": [],
+           "wave_ms": []}
+    for deg in (2, 4, 8, 16, 24, 32, 48, 64, 128):
+        real = PairList(ring_list(n, deg), n).on("cuda")
+        w = torch.randn((T, real.n_pairs), device="cuda", dtype=x.dtype)
+        rec["degree"].append(deg)
+        for form, fake in (("lane", 0), ("wave", 1 << 30)):
+            tab = K.PairTables(real.pairs, real.a_ptr, real.a_idx, real.b_ptr, real.b_idx, fake, fake, n, n)
+            rec[form + "_ms"].append(median_ms(lambda: K.pair_list_pull(w, x, x, tab), reps))
+        del w
+    return rec
+
+
+def pairlist_rows(args):
+    import numpy as np
+    import torch
+
+    for name, T, _, n, dt in CASES:
+        if args.cases and name not in args.cases:
+            continue
+        rec, x = list_kernel_row("triangle_" + name, "triangle", np.stack(np.triu_indices(n, 1), axis=1), T, n, dt, args.reps)
+        if not args.no_end_to_end:
+            rec.update(triangle_end_to_end(x, args.reps, args.parent))
+        print(json.dumps(rec), flush=True)
+        del x
+        torch.cuda.empty_cache()
+    for dt in ("f32", "f64"):
+        rec, _ = list_kernel_row("bonded_n256_" + dt, "chain + 1-3 + 1-4", bonded_list(256), 10000, 256, dt, args.reps,
+                                 matrix=False)
+        print(json.dumps(rec), flush=True)
+        print(json.dumps(form_sweep(10000, 256, dt, args.reps)), flush=True)
+
+
 def child(args):
     """One dispatch of every op, --reps times, cases and ops in order (the rocprofv3 run)."""
     import torch
@@ -195,9 +349,14 @@ def main():
     ap.add_argument("--rocprof-timeout", type=int, default=600)
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--pairlist", action="store_true", help="the K9c / K9d rows instead (device events)")
+    ap.add_argument("--parent", default="", help="8-character hash of the commit whose triangle route is compared")
     args = ap.parse_args()
     if args.child:
         child(args)
+        return
+    if args.pairlist:
+        pairlist_rows(args)
         return
     import torch
 
