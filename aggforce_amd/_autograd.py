@@ -302,96 +302,117 @@ def _tables(plist, like: torch.Tensor) -> "K.PairTables":
     return plist.on(like.device) if hasattr(plist, "on") else plist
 
 
+def _box_kw(box, ct: torch.dtype) -> dict:
+    """The ``box`` keyword of a kernel call in the call's dtype; with no box, no keyword (the open call as it was)."""
+    if box is None:
+        return {}
+    if box.requires_grad:
+        raise ValueError("box is a constant: gradients with respect to box lengths are not built")
+    return {"box": _widened(box, ct)}
+
+
 class PairListDist(torch.autograd.Function):
     """D[t,p] = |X[t,j_p] - C[t,i_p]| (``square``: squared) over the pairs of ``plist`` on K9c
-    (``aggf_pair_list_dist``), in the promoted dtype.  The backward is PairDist's with the list forms."""
+    (``aggf_pair_list_dist``), in the promoted dtype.  The backward is PairDist's with the list forms.
+
+    ``box`` ((3,) or (T, 3) tensor on the operands' device, a constant): every displacement of coordinates is its
+    minimum image under that box (the box forms of K9c / K9d).  The wrap is locally constant, so a derivative differs
+    from the open one only in the displacement it multiplies: the box goes to every call that forms a displacement of
+    coordinates, and the pulls whose "sites" are tangents (``PairListPull`` / ``PairListDot`` backward) stay open --
+    differences of tangents are not displacements and are never wrapped."""
 
     @staticmethod
-    def forward(ctx, X, C, plist, square=False):
+    def forward(ctx, X, C, plist, square=False, box=None):
         ct = _pair_dtype(X, C)
-        D = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_SQDIST if square else K.PAIR_DIST)
-        ctx.square, ctx.plist = bool(square), plist
+        D = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_SQDIST if square else K.PAIR_DIST,
+                             **_box_kw(box, ct))
+        ctx.square, ctx.plist, ctx.box = bool(square), plist, box
         ctx.save_for_backward(X, C, D)
         return D
 
     @staticmethod
     def backward(ctx, H):
         X, C, D = ctx.saved_tensors
-        plist = ctx.plist
+        plist, box = ctx.plist, ctx.box
         want_x, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (want_x or want_c):
-            return None, None, None, None
-        if ctx.square:
+            return None, None, None, None, None
+        if ctx.square and box is not None:  # (2 u, not the image of 2 X - 2 C)
+            dX, dC = PairListPull.apply(2 * H, X, C, plist, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c),
+                                        box)
+        elif ctx.square:
             dX, dC = PairListPull.apply(H, 2 * X, 2 * C, plist, want_x, want_c,
                                         _pull_dtype(D.dtype, X, C, want_x, want_c))
         elif torch.is_grad_enabled():
             pos = D > 0
             W = torch.where(pos, H / torch.where(pos, D, torch.ones_like(D)), torch.zeros_like(D))
-            dX, dC = PairListPull.apply(W, X, C, plist, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c))
+            dX, dC = PairListPull.apply(W, X, C, plist, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c),
+                                        box)
         else:
             ct = _pair_dtype(H, D)
             dX, dC = K.pair_list_pull(_widened(H, ct), _widened(X, ct), _widened(C, ct), _tables(plist, X),
                                       dv=_widened(D, ct), want_a=want_x, want_b=want_c,
-                                      out_dtype=_pull_dtype(ct, X, C, want_x, want_c))
-        return _as(dX, X.dtype), _as(dC, C.dtype), None, None
+                                      out_dtype=_pull_dtype(ct, X, C, want_x, want_c), **_box_kw(box, ct))
+        return _as(dX, X.dtype), _as(dC, C.dtype), None, None, None
 
 
 class PairListPull(torch.autograd.Function):
     """(A, B), A[t,j,:] = sum_{p: j_p = j} W[t,p] u[t,p] and B[t,i,:] = -sum_{p: i_p = i} W[t,p] u[t,p], on K9d
     (``aggf_pair_list_pull``), in ``out_dtype`` (default: promoted).  ``want_a`` / ``want_b`` False: that output is
-    None."""
+    None.  ``box``: u is the minimum image of X[t,j_p] - C[t,i_p] (see ``PairListDist``)."""
 
     @staticmethod
-    def forward(ctx, W, X, C, plist, want_a=True, want_b=True, out_dtype=None):
+    def forward(ctx, W, X, C, plist, want_a=True, want_b=True, out_dtype=None, box=None):
         ct = _pair_dtype(W, X, C) if out_dtype is None else torch.promote_types(_pair_dtype(W, X, C), out_dtype)
         A, B = K.pair_list_pull(_widened(W, ct), _widened(X, ct), _widened(C, ct), _tables(plist, X), want_a=want_a,
-                                want_b=want_b, out_dtype=out_dtype or ct)
-        ctx.plist = plist
+                                want_b=want_b, out_dtype=out_dtype or ct, **_box_kw(box, ct))
+        ctx.plist, ctx.box = plist, box
         ctx.save_for_backward(W, X, C)
         return A, B
 
     @staticmethod
     def backward(ctx, GA, GB):
         W, X, C = ctx.saved_tensors
-        plist = ctx.plist
+        plist, box = ctx.plist, ctx.box
         dW = dX = dC = None
         if GA is None and GB is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         ct = _pair_dtype(W, X, C, *(g for g in (GA, GB) if g is not None))
         GA, GB = _zeros_if_none(GA, X, ct), _zeros_if_none(GB, C, ct)
         if ctx.needs_input_grad[0]:
-            dW = _as(PairListDot.apply(GA, GB, X, C, plist), W.dtype)
+            dW = _as(PairListDot.apply(GA, GB, X, C, plist, box), W.dtype)
         want_x, want_c = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if want_x or want_c:
+        if want_x or want_c:  # (sums of W (GA_j - GB_i): tangents, open under any box)
             dX, dC = PairListPull.apply(W, GA, GB, plist, want_x, want_c, _pull_dtype(ct, X, C, want_x, want_c))
-        return dW, _as(dX, X.dtype), _as(dC, C.dtype), None, None, None, None
+        return dW, _as(dX, X.dtype), _as(dC, C.dtype), None, None, None, None, None
 
 
 class PairListDot(torch.autograd.Function):
     """out[t,p] = (V[t,j_p] - Y[t,i_p]) . (X[t,j_p] - C[t,i_p]) on K9c (``aggf_pair_list_dist``, DOT), in the promoted
-    dtype."""
+    dtype.  ``box``: the second factor is its minimum image; V - Y is never wrapped (see ``PairListDist``)."""
 
     @staticmethod
-    def forward(ctx, V, Y, X, C, plist):
+    def forward(ctx, V, Y, X, C, plist, box=None):
         ct = _pair_dtype(V, Y, X, C)
         out = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_DOT, _widened(V, ct),
-                               _widened(Y, ct))
-        ctx.plist = plist
+                               _widened(Y, ct), **_box_kw(box, ct))
+        ctx.plist, ctx.box = plist, box
         ctx.save_for_backward(V, Y, X, C)
         return out
 
     @staticmethod
     def backward(ctx, H):
         V, Y, X, C = ctx.saved_tensors
-        plist = ctx.plist
+        plist, box = ctx.plist, ctx.box
         need = ctx.needs_input_grad
         dV = dY = dX = dC = None
         ct = _pair_dtype(H, V, Y, X, C)
         if need[0] or need[1]:
-            dV, dY = PairListPull.apply(H, X, C, plist, need[0], need[1], _pull_dtype(ct, V, Y, need[0], need[1]))
-        if need[2] or need[3]:
+            dV, dY = PairListPull.apply(H, X, C, plist, need[0], need[1], _pull_dtype(ct, V, Y, need[0], need[1]),
+                                        box)
+        if need[2] or need[3]:  # (sums of H (V_j - Y_i): tangents, open under any box)
             dX, dC = PairListPull.apply(H, V, Y, plist, need[2], need[3], _pull_dtype(ct, X, C, need[2], need[3]))
-        return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype), None
+        return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype), None, None
 
 
 # ------------------------------------------------------------------ Gaussian radial basis (K10)

@@ -1236,11 +1236,26 @@ def _pair_list_sites(name: str, x: torch.Tensor, c: torch.Tensor, tab: PairTable
     return T, m, n, tab.n_pairs
 
 
+def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor) -> int:
+    """The element stride between the frames of ``box``: 3 for (T, 3), 0 for (3,); a contiguous tensor in the dtype
+    and on the device of ``x``."""
+    T = x.shape[0]
+    if (not isinstance(box, torch.Tensor) or box.dtype != x.dtype or box.device != x.device or not box.is_contiguous()
+            or tuple(box.shape) not in ((3,), (T, 3))):
+        raise ValueError(f"{name}: box must be a contiguous {x.dtype} tensor of shape (3,) or ({T}, 3) on {x.device}; "
+                         f"got {tuple(box.shape) if hasattr(box, 'shape') else type(box)} "
+                         f"{getattr(box, 'dtype', '')} on {getattr(box, 'device', '')}")
+    return 3 if box.dim() == 2 else 0
+
+
 def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int = PAIR_DIST,
-                   v: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   v: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                   box: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(T, P) in the operands' dtype over u[t,p] = x[t,j_p] - c[t,i_p] (aggf_pair_list_dist): |u|, u.u or
-    (v[t,j_p] - y[t,i_p]).u by ``mode``, as ``pair_dist``."""
+    (v[t,j_p] - y[t,i_p]).u by ``mode``, as ``pair_dist``.  ``box`` ((3,) or (T, 3), the operands' dtype): u is its
+    minimum image under that orthorhombic box (aggf_pair_list_dist_pbc); v - y is never wrapped."""
     T, m, n, P = _pair_list_sites("pair_list_dist", x, c, tab)
+    stride = None if box is None else _box_arg("pair_list_dist", box, x)
     if mode not in (PAIR_DIST, PAIR_SQDIST, PAIR_DOT):
         raise ValueError(f"pair_list_dist: mode {mode}")
     if mode == PAIR_DOT:
@@ -1252,19 +1267,25 @@ def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int 
     if out.numel() == 0:
         return out
     with _timed("pair_list_dist"):
-        check(lib().aggf_pair_list_dist(ptr(x), ptr(c), ptr(v), ptr(y), ptr(tab.pairs), T, m, n, P,
-                                        dtype_code(x.dtype), mode, ptr(out), stream_ptr()), "aggf_pair_list_dist")
+        if box is None:
+            check(lib().aggf_pair_list_dist(ptr(x), ptr(c), ptr(v), ptr(y), ptr(tab.pairs), T, m, n, P,
+                                            dtype_code(x.dtype), mode, ptr(out), stream_ptr()), "aggf_pair_list_dist")
+        else:
+            check(lib().aggf_pair_list_dist_pbc(ptr(x), ptr(c), ptr(v), ptr(y), ptr(tab.pairs), T, m, n, P,
+                                                dtype_code(x.dtype), mode, ptr(box), stride, ptr(out), stream_ptr()),
+                  "aggf_pair_list_dist_pbc")
     return out
 
 
 def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairTables,
                    dv: Optional[torch.Tensor] = None, want_a: bool = True, want_b: bool = True,
-                   out_dtype: Optional[torch.dtype] = None):
+                   out_dtype: Optional[torch.dtype] = None, box: Optional[torch.Tensor] = None):
     """(A, B): A[t,j,:] = sum_{p: j_p = j} w_p u_p (T, n, 3) and B[t,i,:] = -sum_{p: i_p = i} w_p u_p (T, m, 3) over
     u[t,p] = x[t,j_p] - c[t,i_p], with the weights w (T, P) or, given ``dv``, (dv > 0 ? w / dv : 0)
     (aggf_pair_list_pull).  An output that is not wanted is None and costs nothing.  All operands share a dtype at
-    least as wide as out_dtype (default: theirs)."""
+    least as wide as out_dtype (default: theirs).  ``box``: as ``pair_list_dist`` (aggf_pair_list_pull_pbc)."""
     T, m, n, P = _pair_list_sites("pair_list_pull", x, c, tab)
+    stride = None if box is None else _box_arg("pair_list_pull", box, x)
     out_dtype = out_dtype or x.dtype
     for name, arr in (("w", w), ("dv", dv)):
         if arr is not None and (tuple(arr.shape) != (T, P) or arr.dtype != x.dtype or not arr.is_contiguous()):
@@ -1279,11 +1300,38 @@ def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairT
     if not (want_a or want_b):
         return None, None
     with _timed("pair_list_pull"):
-        check(lib().aggf_pair_list_pull(ptr(w), ptr(dv), ptr(x), ptr(c), ptr(tab.pairs), ptr(tab.a_ptr),
-                                        ptr(tab.a_idx), ptr(tab.b_ptr), ptr(tab.b_idx), tab.max_deg_a, tab.max_deg_b,
-                                        T, m, n, P, dtype_code(x.dtype), ptr(a), ptr(b), dtype_code(out_dtype),
-                                        stream_ptr()), "aggf_pair_list_pull")
+        if box is None:
+            check(lib().aggf_pair_list_pull(ptr(w), ptr(dv), ptr(x), ptr(c), ptr(tab.pairs), ptr(tab.a_ptr),
+                                            ptr(tab.a_idx), ptr(tab.b_ptr), ptr(tab.b_idx), tab.max_deg_a,
+                                            tab.max_deg_b, T, m, n, P, dtype_code(x.dtype), ptr(a), ptr(b),
+                                            dtype_code(out_dtype), stream_ptr()), "aggf_pair_list_pull")
+        else:
+            check(lib().aggf_pair_list_pull_pbc(ptr(w), ptr(dv), ptr(x), ptr(c), ptr(tab.pairs), ptr(tab.a_ptr),
+                                                ptr(tab.a_idx), ptr(tab.b_ptr), ptr(tab.b_idx), tab.max_deg_a,
+                                                tab.max_deg_b, T, m, n, P, dtype_code(x.dtype), ptr(box), stride,
+                                                ptr(a), ptr(b), dtype_code(out_dtype), stream_ptr()),
+                  "aggf_pair_list_pull_pbc")
     return a, b
+
+
+def pair_min(x: torch.Tensor, c: torch.Tensor, square: bool = False, box: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(m, n) in the operands' dtype: out[i,j] = min_t |x[t,j] - c[t,i]| (``square``: squared), the minimum image
+    under ``box`` if given (aggf_pair_min, K9e).  A NaN distance makes its pair NaN; without frames every minimum is
+    +inf (the empty minimum)."""
+    T, m, n = _pair_sites("pair_min", x, c)
+    stride = 0 if box is None else _box_arg("pair_min", box, x)
+    if T == 0:
+        return torch.full((m, n), float("inf"), dtype=x.dtype, device=x.device)
+    out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+    if out.numel() == 0:
+        return out
+    l = lib()
+    need = l.aggf_pair_min_workspace_bytes(T, m, n, dtype_code(x.dtype))
+    ws = workspace(need, x.device, "pairmin") if need else None
+    with _timed("pair_min"):
+        check(l.aggf_pair_min(ptr(x), ptr(c), T, m, n, dtype_code(x.dtype), ptr(box), stride, int(bool(square)),
+                              ptr(out), ptr(ws), need, stream_ptr()), "aggf_pair_min")
+    return out
 
 
 # ------------------------------------------------------------------ K10 Gaussian radial basis (aggforce_amd/_autograd.py)

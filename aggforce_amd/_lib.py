@@ -78,6 +78,12 @@ PROTOTYPES = {
     "aggf_pair_list_dist": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, C.c_int, C.c_int, _vp, _vp]),
     "aggf_pair_list_pull": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64,
                                       C.c_int, _vp, _vp, C.c_int, _vp]),
+    "aggf_pair_list_dist_pbc": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, C.c_int, C.c_int, _vp, _i32, _vp,
+                                          _vp]),
+    "aggf_pair_list_pull_pbc": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64,
+                                          C.c_int, _vp, _i32, _vp, _vp, C.c_int, _vp]),
+    "aggf_pair_min_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
+    "aggf_pair_min": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _i32, C.c_int, _vp, _vp, _sz, _vp]),
     "aggf_gbasis_expand": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _dbl, _dbl, _i32, C.c_int, _vp, _vp]),
     "aggf_gbasis_contract": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _dbl, _dbl, _i32, C.c_int, _vp, _vp]),
     "aggf_gbasis_sum_workspace_bytes": (_sz, [_i64, _i32, _i32]),

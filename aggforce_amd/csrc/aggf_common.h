@@ -199,6 +199,37 @@ __device__ __forceinline__ T pair_element(T d0, T d1, T d2, T e0, T e1, T e2) {
   return MODE == AGGF_PAIR_DIST ? sqrt(val) : val;
 }
 
+// ---- minimum image of one displacement component under an orthorhombic box of length L (invL = T(1) / L, formed once
+// per frame and dimension by box_lengths): the one wrap of every box kernel (K9c / K9d box forms, K9e), its roundings
+// written out for the reason pair_dot3's are.  k = rint(d invL), u = fma(-k, L, d).  rint rounds to nearest even (one
+// v_rndne) and is odd, so min_image(-d) == -min_image(d) exactly; where |d| << L, k is 0 and u is d bit for bit.
+__device__ __forceinline__ float min_image(float d, float L, float invL) {
+#pragma clang fp contract(off)
+  const float k = __builtin_rintf(d * invL);
+  return __builtin_fmaf(-k, L, d);
+}
+__device__ __forceinline__ double min_image(double d, double L, double invL) {
+#pragma clang fp contract(off)
+  const double k = __builtin_rint(d * invL);
+  return __builtin_fma(-k, L, d);
+}
+// The three lengths of one frame's box and their inverses.  A length that is not a positive finite number becomes NaN
+// (and so does everything wrapped with it: the convention a bad pair index has, at no host synchronisation for a box
+// that lives on the device); returns whether all three are good.
+template <typename T>
+__device__ __forceinline__ bool box_lengths(const T* __restrict__ box, T L[3], T invL[3]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const T l = box[k];
+    const bool good = l > (T)0 && l < (T)__builtin_inf();
+    L[k] = good ? l : (T)__builtin_nan("");
+    invL[k] = (T)1 / L[k];
+    ok = ok && good;
+  }
+  return ok;
+}
+
 // ---- Philox4x32-10 (Salmon et al., SC'11): counter = 64-bit quad index, key = seed ----
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;

@@ -7,6 +7,9 @@
 //                                   (Own = X, Oth = C) that is A[t,j,:] = sum w u, with the table by i (Own = C,
 //                                   Oth = X) it is B[t,i,:] = -sum w u (-(a - b) is b - a exactly); w = W or
 //                                   (Dv > 0 ? W / Dv : 0)
+//   pairlist_pbc_kernel, pairlist_pull_pbc_kernel: the same two with u replaced by its minimum image under an
+//                                   orthorhombic box per frame (min_image, aggf_common.h).  Each pair of kernels shares
+//                                   one __device__ body; the open ones keep their names, arguments and bits.
 //
 // The arrays of a call are T P elements where K9a / K9b move T m n.  No atomics: a site's sum walks its entries of the
 // incidence table (CSR: ptr, pair index, ascending pair index), so results are bit-identical run to run.  Element
@@ -26,11 +29,16 @@ namespace aggf {
 constexpr int PL_MIN_FRAMES = 8;
 constexpr int64_t PL_TARGET_TASKS = 16384;
 
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) void pairlist_kernel(const T* __restrict__ X, const T* __restrict__ C,
-                                                       const T* __restrict__ V, const T* __restrict__ Y,
-                                                       const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
-                                                       int32_t n, int64_t P, int64_t frames, T* __restrict__ out) {
+//
+// PBC: u is wrapped to its minimum image under the frame's box (min_image; `box` (T, 3) with bstride 3, or (3,) with
+// bstride 0: a frame's three lengths are wave-uniform and read once per frame, once per task for a constant box).  The
+// tangent operands V - Y of DOT are never wrapped: the wrap is locally constant in X and C.
+template <typename T, int MODE, bool PBC>
+__device__ __forceinline__ void pairlist_body(const T* __restrict__ X, const T* __restrict__ C,
+                                              const T* __restrict__ V, const T* __restrict__ Y,
+                                              const int32_t* __restrict__ pairs, int64_t nT, int32_t m, int32_t n,
+                                              int64_t P, int64_t frames, const T* __restrict__ box, int32_t bstride,
+                                              T* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t pblocks = (P + 63) / 64, fblocks = (nT + frames - 1) / frames;
@@ -52,9 +60,15 @@ __global__ __launch_bounds__(256) void pairlist_kernel(const T* __restrict__ X, 
     const T* c = C + co;
     const T* v = MODE == AGGF_PAIR_DOT ? V + xo : nullptr;
     const T* y = MODE == AGGF_PAIR_DOT ? Y + co : nullptr;
+    T L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
+    if (PBC && bstride == 0) box_lengths(box, L, iL);
 #pragma unroll 4
     for (int64_t t = t0; t < t1; ++t, x += xs, c += cs, o += P) {
-      const T d0 = x[0] - c[0], d1 = x[1] - c[1], d2 = x[2] - c[2];
+      T d0 = x[0] - c[0], d1 = x[1] - c[1], d2 = x[2] - c[2];
+      if (PBC) {
+        if (bstride != 0) box_lengths(box + t * bstride, L, iL);
+        d0 = min_image(d0, L[0], iL[0]), d1 = min_image(d1, L[1], iL[1]), d2 = min_image(d2, L[2], iL[2]);
+      }
       T e0 = 0, e1 = 0, e2 = 0;
       if (MODE == AGGF_PAIR_DOT) {
         e0 = v[0] - y[0], e1 = v[1] - y[1], e2 = v[2] - y[2];
@@ -63,6 +77,24 @@ __global__ __launch_bounds__(256) void pairlist_kernel(const T* __restrict__ X, 
       *o = pair_element<T, MODE>(d0, d1, d2, e0, e1, e2);
     }
   }
+}
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void pairlist_kernel(const T* __restrict__ X, const T* __restrict__ C,
+                                                       const T* __restrict__ V, const T* __restrict__ Y,
+                                                       const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
+                                                       int32_t n, int64_t P, int64_t frames, T* __restrict__ out) {
+  pairlist_body<T, MODE, false>(X, C, V, Y, pairs, nT, m, n, P, frames, nullptr, 0, out);
+}
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void pairlist_pbc_kernel(const T* __restrict__ X, const T* __restrict__ C,
+                                                           const T* __restrict__ V, const T* __restrict__ Y,
+                                                           const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
+                                                           int32_t n, int64_t P, int64_t frames,
+                                                           const T* __restrict__ box, int32_t bstride,
+                                                           T* __restrict__ out) {
+  pairlist_body<T, MODE, true>(X, C, V, Y, pairs, nT, m, n, P, frames, box, bstride, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -91,13 +123,16 @@ __device__ __forceinline__ TI pull_weight(const TI* __restrict__ W, const TI* __
   return wv;
 }
 
-template <typename TI, typename TO, bool HAS_DV, int FORM>
-__global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict__ W, const TI* __restrict__ Dv,
-                                                            const TI* __restrict__ Own, const TI* __restrict__ Oth,
-                                                            const int32_t* __restrict__ pairs, int32_t ocol,
-                                                            const int32_t* __restrict__ ptr,
-                                                            const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
-                                                            int32_t no, int64_t P, TO* __restrict__ out) {
+// PBC: Own - Oth is wrapped to its minimum image under the frame's box, as in K9c (min_image is odd, so B is still
+// exactly the sum of -w u); a frame whose box is bad gets NaN sums, sites without entries included.
+template <typename TI, typename TO, bool HAS_DV, int FORM, bool PBC>
+__device__ __forceinline__ void pairlist_pull_body(const TI* __restrict__ W, const TI* __restrict__ Dv,
+                                                   const TI* __restrict__ Own, const TI* __restrict__ Oth,
+                                                   const int32_t* __restrict__ pairs, int32_t ocol,
+                                                   const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                                                   int64_t nT, int32_t ns, int32_t no, int64_t P,
+                                                   const TI* __restrict__ box, int32_t bstride,
+                                                   TO* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t ntask = nT * ns;
   const int64_t first = FORM == PLP_LANE ? (int64_t)blockIdx.x * 256 + threadIdx.x
@@ -113,7 +148,10 @@ __global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict
     int64_t beg = ptr[s], end = ptr[s + 1];  // (a run is clipped to the P entries the table has)
     beg = beg < 0 ? 0 : beg;
     end = end > P ? P : end;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    TI L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
+    const bool box_ok = PBC ? box_lengths(box + t * bstride, L, iL) : true;
+    const double zero = box_ok ? 0.0 : __builtin_nan("");
+    double a0 = zero, a1 = zero, a2 = zero;
     for (int64_t e = FORM == PLP_LANE ? beg : beg + lane; e < end; e += FORM == PLP_LANE ? 1 : 64) {
       const int32_t p = idx[e];
       if (!((uint32_t)p < (uint64_t)P)) continue;
@@ -121,7 +159,9 @@ __global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict
       if (!((uint32_t)o < (uint32_t)no)) continue;
       const TI wv = pull_weight<TI, HAS_DV>(w, dv, p);
       const TI* r = oth + 3 * (int64_t)o;
-      a0 += (double)(wv * (o0 - r[0])), a1 += (double)(wv * (o1 - r[1])), a2 += (double)(wv * (o2 - r[2]));
+      TI u0 = o0 - r[0], u1 = o1 - r[1], u2 = o2 - r[2];
+      if (PBC) u0 = min_image(u0, L[0], iL[0]), u1 = min_image(u1, L[1], iL[1]), u2 = min_image(u2, L[2], iL[2]);
+      a0 += (double)(wv * u0), a1 += (double)(wv * u1), a2 += (double)(wv * u2);
     }
     if (FORM == PLP_WAVE) {
 #pragma unroll
@@ -134,6 +174,27 @@ __global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict
       dst[0] = (TO)a0, dst[1] = (TO)a1, dst[2] = (TO)a2;
     }
   }
+}
+
+template <typename TI, typename TO, bool HAS_DV, int FORM>
+__global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict__ W, const TI* __restrict__ Dv,
+                                                            const TI* __restrict__ Own, const TI* __restrict__ Oth,
+                                                            const int32_t* __restrict__ pairs, int32_t ocol,
+                                                            const int32_t* __restrict__ ptr,
+                                                            const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
+                                                            int32_t no, int64_t P, TO* __restrict__ out) {
+  pairlist_pull_body<TI, TO, HAS_DV, FORM, false>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, nullptr, 0, out);
+}
+
+template <typename TI, typename TO, bool HAS_DV, int FORM>
+__global__ __launch_bounds__(256) void pairlist_pull_pbc_kernel(const TI* __restrict__ W, const TI* __restrict__ Dv,
+                                                                const TI* __restrict__ Own, const TI* __restrict__ Oth,
+                                                                const int32_t* __restrict__ pairs, int32_t ocol,
+                                                                const int32_t* __restrict__ ptr,
+                                                                const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
+                                                                int32_t no, int64_t P, const TI* __restrict__ box,
+                                                                int32_t bstride, TO* __restrict__ out) {
+  pairlist_pull_body<TI, TO, HAS_DV, FORM, true>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box, bstride, out);
 }
 
 static inline dim3 pairlist_grid(int64_t blocks) {
@@ -154,12 +215,24 @@ static int pairlist_shape(const char* who, int64_t T, int32_t m, int32_t n, int6
   return AGGF_OK;
 }
 
+// (box NULL: the open kernels, with the arguments they have always had)
 template <typename T>
 static void launch_pairlist(int mode, dim3 grid, hipStream_t stream, const void* X, const void* C, const void* V,
                             const void* Y, const int32_t* pairs, int64_t nT, int32_t m, int32_t n, int64_t P,
-                            int64_t frames, void* out) {
+                            int64_t frames, const void* box, int32_t bstride, void* out) {
   const dim3 block(256);
-  if (mode == AGGF_PAIR_DIST)
+  if (box) {
+#define AGGF_PL_PBC(MODE)                                                                                       \
+  AGGF_LAUNCH((pairlist_pbc_kernel<T, MODE>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,    \
+              (const T*)Y, pairs, nT, m, n, P, frames, (const T*)box, bstride, (T*)out)
+    if (mode == AGGF_PAIR_DIST)
+      AGGF_PL_PBC(AGGF_PAIR_DIST);
+    else if (mode == AGGF_PAIR_SQDIST)
+      AGGF_PL_PBC(AGGF_PAIR_SQDIST);
+    else
+      AGGF_PL_PBC(AGGF_PAIR_DOT);
+#undef AGGF_PL_PBC
+  } else if (mode == AGGF_PAIR_DIST)
     AGGF_LAUNCH((pairlist_kernel<T, AGGF_PAIR_DIST>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,
                 (const T*)Y, pairs, nT, m, n, P, frames, (T*)out);
   else if (mode == AGGF_PAIR_SQDIST)
@@ -173,10 +246,19 @@ static void launch_pairlist(int mode, dim3 grid, hipStream_t stream, const void*
 template <typename TI, typename TO, bool HAS_DV>
 static void launch_pull_form(int form, hipStream_t stream, const void* W, const void* Dv, const void* Own,
                              const void* Oth, const int32_t* pairs, int32_t ocol, const int32_t* ptr,
-                             const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, void* out) {
+                             const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, const void* box,
+                             int32_t bstride, void* out) {
   const dim3 block(256);
   const int64_t tasks = nT * ns;
-  if (form == PLP_LANE)
+  if (box && form == PLP_LANE)
+    AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_LANE>), pairlist_grid(ceil_div(tasks, 256)), block, 0,
+                stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
+                P, (const TI*)box, bstride, (TO*)out);
+  else if (box)
+    AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_WAVE>), pairlist_grid(ceil_div(tasks, 4)), block, 0,
+                stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
+                P, (const TI*)box, bstride, (TO*)out);
+  else if (form == PLP_LANE)
     AGGF_LAUNCH((pairlist_pull_kernel<TI, TO, HAS_DV, PLP_LANE>), pairlist_grid(ceil_div(tasks, 256)), block, 0, stream,
                 (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no, P,
                 (TO*)out);
@@ -189,12 +271,15 @@ static void launch_pull_form(int form, hipStream_t stream, const void* W, const 
 // the sums of one table (nothing to do without sites)
 static void launch_pull(int in_dtype, int out_dtype, int32_t max_deg, hipStream_t stream, const void* W, const void* Dv,
                         const void* Own, const void* Oth, const int32_t* pairs, int32_t ocol, const int32_t* ptr,
-                        const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, void* out) {
+                        const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, const void* box,
+                        int32_t bstride, void* out) {
   if (ns == 0) return;
   const int form = max_deg > PLP_LANE_DEG ? PLP_WAVE : PLP_LANE;
 #define AGGF_PULL_FORM(TI, TO)                                                                                       \
-  (Dv ? launch_pull_form<TI, TO, true>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, out)     \
-      : launch_pull_form<TI, TO, false>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, out))
+  (Dv ? launch_pull_form<TI, TO, true>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box,     \
+                                       bstride, out)                                                                 \
+      : launch_pull_form<TI, TO, false>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box,    \
+                                        bstride, out))
   if (in_dtype == AGGF_F32)
     AGGF_PULL_FORM(float, float);
   else if (out_dtype == AGGF_F32)
@@ -204,23 +289,26 @@ static void launch_pull(int in_dtype, int out_dtype, int32_t max_deg, hipStream_
 #undef AGGF_PULL_FORM
 }
 
-}  // namespace aggf
+// the box of a box form: (T, 3) or (3,) in the operands' dtype
+static int pairlist_box(const char* who, const void* box, int32_t box_stride) {
+  if (!box) return fail(AGGF_ERR_ARG, "%s: NULL box", who);
+  if (box_stride != 0 && box_stride != 3) return fail(AGGF_ERR_ARG, "%s: box_stride %d is neither 0 nor 3", who, box_stride);
+  return AGGF_OK;
+}
 
-using namespace aggf;
-
-extern "C" int aggf_pair_list_dist(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
-                                   int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, void* out,
-                                   void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
+// K9c, open (box NULL) or under a box: one launch plan for both
+static int pair_list_dist(const char* who, const void* X, const void* C, const void* V, const void* Y,
+                          const int32_t* pairs, int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode,
+                          const void* box, int32_t box_stride, void* out, hipStream_t stream) {
   int64_t count = 0;
-  const int rc = pairlist_shape("aggf_pair_list_dist", T, m, n, P, &count);
+  const int rc = pairlist_shape(who, T, m, n, P, &count);
   if (rc != AGGF_OK) return rc;
-  if (dtype != AGGF_F32 && dtype != AGGF_F64) return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: bad dtype");
+  if (dtype != AGGF_F32 && dtype != AGGF_F64) return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
   if (mode != AGGF_PAIR_DIST && mode != AGGF_PAIR_SQDIST && mode != AGGF_PAIR_DOT)
-    return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: bad mode");
+    return fail(AGGF_ERR_ARG, "%s: bad mode", who);
   if (count == 0) return AGGF_OK;
-  if (!X || !C || !pairs || !out) return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: NULL pointer");
-  if (mode == AGGF_PAIR_DOT && (!V || !Y)) return fail(AGGF_ERR_ARG, "aggf_pair_list_dist: DOT needs V and Y");
+  if (!X || !C || !pairs || !out) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if (mode == AGGF_PAIR_DOT && (!V || !Y)) return fail(AGGF_ERR_ARG, "%s: DOT needs V and Y", who);
   // a wave walks all frames of its 64 pairs unless that leaves the chip short of tasks
   const int64_t pblocks = ceil_div(P, 64);
   int64_t frames = T;
@@ -228,11 +316,59 @@ extern "C" int aggf_pair_list_dist(const void* X, const void* C, const void* V, 
   const int64_t waves = pblocks * ceil_div(T, frames);  // <= count
   const dim3 grid = pairlist_grid(ceil_div(waves, 4));
   if (dtype == AGGF_F64)
-    launch_pairlist<double>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, out);
+    launch_pairlist<double>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, box, box_stride, out);
   else
-    launch_pairlist<float>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, out);
+    launch_pairlist<float>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, box, box_stride, out);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
+}
+
+// K9d, open (box NULL) or under a box
+static int pair_list_pull(const char* who, const void* W, const void* Dv, const void* X, const void* C,
+                          const int32_t* pairs, const int32_t* a_ptr, const int32_t* a_idx, const int32_t* b_ptr,
+                          const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m, int32_t n,
+                          int64_t P, int in_dtype, const void* box, int32_t box_stride, void* A, void* B, int out_dtype,
+                          hipStream_t stream) {
+  int64_t count = 0;
+  const int rc = pairlist_shape(who, T, m, n, P, &count);
+  if (rc != AGGF_OK) return rc;
+  if ((in_dtype != AGGF_F32 && in_dtype != AGGF_F64) || (out_dtype != AGGF_F32 && out_dtype != AGGF_F64))
+    return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
+  if (in_dtype == AGGF_F32 && out_dtype == AGGF_F64)
+    return fail(AGGF_ERR_ARG, "%s: float32 inputs with float64 outputs: widen the inputs", who);
+  if (max_deg_a < 0 || max_deg_b < 0) return fail(AGGF_ERR_ARG, "%s: negative degree", who);
+  if (count == 0 || (!A && !B)) return AGGF_OK;
+  if (!W || !X || !C || !pairs) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if ((A && (!a_ptr || !a_idx)) || (B && (!b_ptr || !b_idx)))
+    return fail(AGGF_ERR_ARG, "%s: an output without its incidence table", who);
+  if (A)
+    launch_pull(in_dtype, out_dtype, max_deg_a, stream, W, Dv, X, C, pairs, 0, a_ptr, a_idx, T, n, m, P, box,
+                box_stride, A);
+  if (B)
+    launch_pull(in_dtype, out_dtype, max_deg_b, stream, W, Dv, C, X, pairs, 1, b_ptr, b_idx, T, m, n, P, box,
+                box_stride, B);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+}  // namespace aggf
+
+using namespace aggf;
+
+extern "C" int aggf_pair_list_dist(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
+                                   int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, void* out,
+                                   void* stream_v) {
+  return pair_list_dist("aggf_pair_list_dist", X, C, V, Y, pairs, T, m, n, P, dtype, mode, nullptr, 0, out,
+                        (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_pair_list_dist_pbc(const void* X, const void* C, const void* V, const void* Y,
+                                       const int32_t* pairs, int64_t T, int32_t m, int32_t n, int64_t P, int dtype,
+                                       int mode, const void* box, int32_t box_stride, void* out, void* stream_v) {
+  const int rc = pairlist_box("aggf_pair_list_dist_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return pair_list_dist("aggf_pair_list_dist_pbc", X, C, V, Y, pairs, T, m, n, P, dtype, mode, box, box_stride, out,
+                        (hipStream_t)stream_v);
 }
 
 extern "C" int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void* C, const int32_t* pairs,
@@ -240,21 +376,18 @@ extern "C" int aggf_pair_list_pull(const void* W, const void* Dv, const void* X,
                                    const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m,
                                    int32_t n, int64_t P, int in_dtype, void* A, void* B, int out_dtype,
                                    void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  int64_t count = 0;
-  const int rc = pairlist_shape("aggf_pair_list_pull", T, m, n, P, &count);
+  return pair_list_pull("aggf_pair_list_pull", W, Dv, X, C, pairs, a_ptr, a_idx, b_ptr, b_idx, max_deg_a, max_deg_b, T,
+                        m, n, P, in_dtype, nullptr, 0, A, B, out_dtype, (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_pair_list_pull_pbc(const void* W, const void* Dv, const void* X, const void* C,
+                                       const int32_t* pairs, const int32_t* a_ptr, const int32_t* a_idx,
+                                       const int32_t* b_ptr, const int32_t* b_idx, int32_t max_deg_a,
+                                       int32_t max_deg_b, int64_t T, int32_t m, int32_t n, int64_t P, int in_dtype,
+                                       const void* box, int32_t box_stride, void* A, void* B, int out_dtype,
+                                       void* stream_v) {
+  const int rc = pairlist_box("aggf_pair_list_pull_pbc", box, box_stride);
   if (rc != AGGF_OK) return rc;
-  if ((in_dtype != AGGF_F32 && in_dtype != AGGF_F64) || (out_dtype != AGGF_F32 && out_dtype != AGGF_F64))
-    return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: bad dtype");
-  if (in_dtype == AGGF_F32 && out_dtype == AGGF_F64)
-    return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: float32 inputs with float64 outputs: widen the inputs");
-  if (max_deg_a < 0 || max_deg_b < 0) return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: negative degree");
-  if (count == 0 || (!A && !B)) return AGGF_OK;
-  if (!W || !X || !C || !pairs) return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: NULL pointer");
-  if ((A && (!a_ptr || !a_idx)) || (B && (!b_ptr || !b_idx)))
-    return fail(AGGF_ERR_ARG, "aggf_pair_list_pull: an output without its incidence table");
-  if (A) launch_pull(in_dtype, out_dtype, max_deg_a, stream, W, Dv, X, C, pairs, 0, a_ptr, a_idx, T, n, m, P, A);
-  if (B) launch_pull(in_dtype, out_dtype, max_deg_b, stream, W, Dv, C, X, pairs, 1, b_ptr, b_idx, T, m, n, P, B);
-  AGGF_LAUNCH_OK();
-  return AGGF_OK;
+  return pair_list_pull("aggf_pair_list_pull_pbc", W, Dv, X, C, pairs, a_ptr, a_idx, b_ptr, b_idx, max_deg_a,
+                        max_deg_b, T, m, n, P, in_dtype, box, box_stride, A, B, out_dtype, (hipStream_t)stream_v);
 }

@@ -364,6 +364,75 @@ int main() {
                                            8199 - deg, T, m, n, P, in, sel & 1 ? d : nullptr,
                                            sel & 2 ? d + 4096 : nullptr, od, nullptr));
           }
+  // K9c / K9d box forms: the box's own refusals (NULL, a stride other than 0 or 3), the refusals and empty problems
+  // of the open twins, and the same grid of plausible calls with either stride
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, nullptr, 3, d, nullptr));  // no box
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, p, 1, d, nullptr));        // stride
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, p, -3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(nullptr, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, p, 3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, nullptr, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, p, 0, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, p, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DOT, p, 3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 2, AGGF_PAIR_DIST, p, 3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, 3, p, 3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, -1, 3, 5, 9, 1, AGGF_PAIR_DIST, p, 3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, 7, 3, 5, (int64_t)1 << 31, 1, AGGF_PAIR_DIST, p, 3, d, nullptr));
+  REFUSED(aggf_pair_list_dist_pbc(p, p, nullptr, nullptr, i32, INT64_MAX / 4, 3, 5, 1, 1, AGGF_PAIR_DIST, p, 3, d, nullptr));
+  RUNS(aggf_pair_list_dist_pbc(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 3, 5, 9, 1, AGGF_PAIR_DIST, p, 3, nullptr, nullptr));
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, nullptr, 0, d, d, 1, nullptr));  // no box
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, p, 2, d, d, 1, nullptr));        // stride
+  REFUSED(aggf_pair_list_pull_pbc(nullptr, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, p, 3, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, nullptr, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, p, 3, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, nullptr, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, p, 3, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 0, p, 3, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, i32, i32, i32, i32, -1, 2, 7, 3, 5, 9, 1, p, 3, d, d, 1, nullptr));
+  REFUSED(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, INT64_MAX / 4, 3, 5, 9, 1, p, 3, d, d, 1, nullptr));
+  RUNS(aggf_pair_list_pull_pbc(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 7, 3, 5, 0, 1, p, 0, nullptr, nullptr, 1, nullptr));
+  RUNS(aggf_pair_list_pull_pbc(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, p, 0, nullptr, nullptr, 1, nullptr));  // neither output
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)100000})
+    for (int32_t m : {1, 17, 257})
+      for (int32_t n : {1, 65, 8200})
+        for (int64_t P : {(int64_t)1, (int64_t)65, (int64_t)32640})
+          for (int in = 0; in < 2; ++in)
+            for (int32_t bs : {0, 3}) {
+              for (int mode : {AGGF_PAIR_DIST, AGGF_PAIR_SQDIST, AGGF_PAIR_DOT})
+                RUNS(aggf_pair_list_dist_pbc(p, (char*)p + 4096, p, (char*)p + 4096, i32, T, m, n, P, in, mode, p, bs, d, nullptr));
+              for (int od = 0; od <= in; ++od)
+                for (int sel = 1; sel < 4; ++sel)
+                  for (int32_t deg : {0, 32, 33})
+                    RUNS(aggf_pair_list_pull_pbc(p, sel == 3 ? p : nullptr, p, (char*)p + 4096, i32, i32, i32, i32, i32,
+                                                 deg, 65 - deg, T, m, n, P, in, p, bs, sel & 1 ? d : nullptr,
+                                                 sel & 2 ? d + 4096 : nullptr, od, nullptr));
+            }
+  // K9e: the workspace query over the grid of shapes (overflowing ones included), refusals, empty shapes, and plausible
+  // calls, open and under a box, with the queried workspace (one split and many)
+  for (int64_t T : Ts)
+    for (int32_t N : Ns) sink += aggf_pair_min_workspace_bytes(T, N / 16 + 1, N, 0) + aggf_pair_min_workspace_bytes(T, N, N, 1);
+  sink += aggf_pair_min_workspace_bytes(INT64_MAX, INT32_MAX, INT32_MAX, 1) + aggf_pair_min_workspace_bytes(-1, 5, 300, 0);
+  REFUSED(aggf_pair_min(nullptr, p, 7, 3, 5, 1, nullptr, 0, 0, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_min(p, nullptr, 7, 3, 5, 1, nullptr, 0, 0, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_min(p, p, 7, 3, 5, 1, nullptr, 0, 0, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_pair_min(p, p, 7, 3, 5, 2, nullptr, 0, 0, d, ws, WS, nullptr));           // dtype
+  REFUSED(aggf_pair_min(p, p, 7, 3, 5, 1, p, 1, 0, d, ws, WS, nullptr));                 // stride
+  REFUSED(aggf_pair_min(p, p, -1, 3, 5, 1, nullptr, 0, 0, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_min(p, p, 7, -3, 5, 1, nullptr, 0, 0, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_min(p, p, INT64_MAX / 4, 3, 5, 1, nullptr, 0, 0, d, ws, WS, nullptr));  // T n
+  REFUSED(aggf_pair_min(p, p, 1000, 3, 5, 1, nullptr, 0, 0, d, ws, 0, nullptr));         // split frames, no workspace
+  REFUSED(aggf_pair_min(p, p, 1000, 3, 5, 1, nullptr, 0, 0, d, nullptr, WS, nullptr));
+  REFUSED(aggf_pair_min(p, p, 1000, 3, 5, 1, nullptr, 0, 0, d, (char*)ws + 4, WS - 4, nullptr));  // misaligned partials
+  RUNS(aggf_pair_min(nullptr, nullptr, 0, 3, 5, 1, nullptr, 0, 0, nullptr, nullptr, 0, nullptr));
+  RUNS(aggf_pair_min(nullptr, nullptr, 7, 0, 5, 0, p, 3, 1, nullptr, nullptr, 0, nullptr));
+  RUNS(aggf_pair_min(p, p, 7, 3, 5, 1, nullptr, 0, 0, d, nullptr, 0, nullptr));          // one split: no workspace
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)2000, (int64_t)100000})
+    for (int32_t m : {1, 17, 257, 8200})
+      for (int32_t n : {1, 65, 256, 257, 8200})
+        for (int in = 0; in < 2; ++in) {
+          const size_t wm = aggf_pair_min_workspace_bytes(T, m, n, in);
+          if (wm > WS) continue;
+          for (int sq = 0; sq < 2; ++sq) {
+            RUNS(aggf_pair_min(p, (char*)p + 4096, T, m, n, in, nullptr, 0, sq, d, ws, wm, nullptr));
+            RUNS(aggf_pair_min(p, (char*)p + 4096, T, m, n, in, p, 3 * sq, sq, d, ws, wm, nullptr));
+          }
+        }
   // K10: the partials' size over the grid of shapes (absurd ones give 0), refusals (NULL pointers, bad dtype / width /
   // clip / order / form, rows or outputs that do not fit, slot tables that do not match the form, short or misaligned
   // workspaces), empty shapes, and plausible calls in every dtype / form / slot selection with the queried workspace

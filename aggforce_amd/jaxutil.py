@@ -12,6 +12,11 @@ autograd handles them.
 exclusions, site-to-atom lists) on K9c / K9d through ``PairListDist`` / ``PairListPull`` / ``PairListDot``: every array
 is (T, n_pairs), forward and backward.  The upper triangles of ``distances(x, return_matrix=False)`` are the list
 ``PairList.upper_triangle(n)``, so they never form the (T, n, n) matrix.
+
+Periodic boundaries (not in the reference): ``pair_distances(..., box=)`` and ``distances_in_box`` take the lengths of
+an orthorhombic cell, one box or one per frame, and return minimum-image distances on the box forms of K9c / K9d.
+``min_distances`` reduces a trajectory to the smallest distance each pair reaches (K9e), and
+``PairList.from_cutoff`` builds the static list of the pairs that come within a cutoff from it.
 """
 from typing import Callable, Union
 
@@ -112,6 +117,38 @@ def _incidence(sites: np.ndarray, n: int):
     return ptr, idx, int(counts.max()) if n else 0
 
 
+def _as_box(box, n_steps: int) -> torch.Tensor:
+    """``box`` as a tensor of shape (3,) or (n_steps, 3): the lengths of an orthorhombic cell, one for all frames or
+    one per frame.  A box on the host (a sequence, a NumPy array, a CPU tensor) is checked here -- positive, finite --
+    and comes out as float64; a box on a GPU is taken as it is (no synchronisation: the kernels turn a frame whose
+    box is bad into NaN).  The box is a constant: one that requires a gradient is refused."""
+    if isinstance(box, torch.Tensor):
+        if box.requires_grad:
+            raise ValueError("box is a constant: gradients with respect to box lengths are not built")
+        if not box.dtype.is_floating_point:
+            box = box.double()
+    else:
+        try:
+            box = torch.as_tensor(np.asarray(box, dtype=np.float64))
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"box must hold numbers: {exc}") from None
+    if tuple(box.shape) not in ((3,), (n_steps, 3)):
+        raise ValueError(f"box must have shape (3,) or (n_steps, 3) = ({n_steps}, 3); got {tuple(box.shape)}")
+    if not box.is_cuda:
+        box = box.double()
+        if not bool((torch.isfinite(box) & (box > 0)).all()):
+            raise ValueError("box lengths must be positive and finite")
+    return box
+
+
+def _wrap(disp: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
+    """The minimum image of displacements (T, ..., 3) in plain torch: d - L rint(d / L), rint to nearest even."""
+    L = box.to(device=disp.device, dtype=disp.dtype if disp.dtype.is_floating_point else torch.float64)
+    if L.dim() == 2:
+        L = L.reshape((L.shape[0],) + (1,) * (disp.dim() - 2) + (3,))
+    return disp - L * torch.round(disp / L)
+
+
 class PairList:
     """A static list of site pairs shared by all frames, validated on the host once: ``pairs`` (P, 2) integers (a
     list, a NumPy array or a torch tensor on any device), row p = (i_p, j_p) with ``0 <= j_p < n_sites`` and
@@ -123,6 +160,7 @@ class PairList:
     ascending pair index) that the backward kernel sums over -- is built on first use, once per device."""
 
     _triangles: dict = {}
+    _all: dict = {}
 
     def __init__(self, pairs, n_sites: int, n_cross: Union[int, None] = None):
         if isinstance(pairs, torch.Tensor):
@@ -175,6 +213,48 @@ class PairList:
             cls._triangles[n_sites] = cls(np.stack(np.triu_indices(n_sites, k=1), axis=1), n_sites)
         return cls._triangles[n_sites]
 
+    @classmethod
+    def all_pairs(cls, n_sites: int, n_cross: Union[int, None] = None) -> "PairList":
+        """Every pair (i, j), i over ``n_cross`` sites (None: the self form, i over ``n_sites``, i == j included), in
+        row-major order of (i, j): a (T, P) array over this list is the (T, other, self) matrix of ``distances``
+        reshaped.  One object per shape, kept."""
+        key = (int(n_sites), None if n_cross is None else int(n_cross))
+        if key not in cls._all:
+            if len(cls._all) >= 8:
+                cls._all.pop(next(iter(cls._all)))
+            n, m = key[0], key[0] if key[1] is None else key[1]
+            i, j = np.divmod(np.arange(m * n, dtype=np.int64), max(n, 1))
+            cls._all[key] = cls(np.stack([i, j], axis=1), n, key[1])
+        return cls._all[key]
+
+    @classmethod
+    def from_cutoff(cls, xyz, cutoff: float, cross_xyz=None, box=None, exclude=None) -> "PairList":
+        """The static list of the pairs that come within ``cutoff`` of each other in any frame:
+        ``min_distances(xyz, cross_xyz, box=box) <= cutoff`` (a NaN minimum is never kept).  The self form keeps i < j
+        in the order of ``upper_triangle``; the cross form keeps all (i, j) in row-major order.  ``exclude`` (a
+        ``PairList`` or a (k, 2) integer array): pairs to leave out, e.g. bonded ones; in the self form (i, j) and
+        (j, i) are the same pair.  Under a box the minimum image is only the nearest image up to half a box length:
+        a cutoff beyond half the smallest length of any frame raises ``ValueError``."""
+        cutoff = float(cutoff)
+        if not cutoff >= 0 or not np.isfinite(cutoff):
+            raise ValueError(f"cutoff must be a non-negative finite number; got {cutoff}")
+        dmin = min_distances(xyz, cross_xyz, box=box)
+        if box is not None:
+            lengths = _as_box(box, int(xyz.shape[0]) if hasattr(xyz, "shape") else len(xyz)).detach().cpu().double()
+            if lengths.numel() and not cutoff <= 0.5 * float(lengths.min()):
+                raise ValueError(f"cutoff {cutoff} is beyond half the smallest box length {float(lengths.min())}: the "
+                                 "minimum image is not the nearest image there")
+        keep = (dmin <= cutoff).cpu().numpy()
+        m, n = keep.shape
+        if cross_xyz is None:
+            keep &= np.triu(np.ones((n, n), dtype=bool), k=1)
+        if exclude is not None:
+            ex = exclude.pairs if isinstance(exclude, PairList) else cls(exclude, n, None if cross_xyz is None else m).pairs
+            keep[ex[:, 0], ex[:, 1]] = False
+            if cross_xyz is None:
+                keep[ex[:, 1], ex[:, 0]] = False
+        return cls(np.argwhere(keep), n, None if cross_xyz is None else m)
+
     def tables(self):
         """The incidence tables on the host: ``(by_j, by_i)``, each ``(ptr, pair index, longest run)``."""
         if self._host is None:
@@ -192,7 +272,7 @@ class PairList:
         return self._devices[device]
 
 
-def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False) -> torch.Tensor:
+def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False, box=None) -> torch.Tensor:
     """Differentiable distances over a list of pairs: (n_steps, n_pairs),
     ``out[t, p] = |xyz[t, j_p] - (cross_xyz if given else xyz)[t, i_p]|`` (squared with ``square``), for ``pairs`` a
     ``PairList`` or any (n_pairs, 2) integer array of rows (i_p, j_p) -- the index order of the (T, other, self) result
@@ -200,7 +280,11 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False) -> torch.Te
 
     float32/float64 GPU tensors run on the K9c / K9d kernels (``PairListDist``): nothing of the size of the distance
     matrix is formed, forward or backward, the result is differentiable in both arrays to any order, and a zero
-    distance has gradient 0.  CPU tensors, NumPy inputs and other dtypes take plain torch operations."""
+    distance has gradient 0.  CPU tensors, NumPy inputs and other dtypes take plain torch operations.
+
+    ``box``: the lengths of an orthorhombic periodic cell, (3,) or (n_steps, 3) (a sequence, an array or a tensor; a
+    constant).  Every displacement is then its minimum image, d - L rint(d / L) per component -- the nearest image
+    for distances up to half a box length -- on the box forms of the same kernels."""
     def shape_of(a):
         return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
 
@@ -215,11 +299,16 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False) -> torch.Te
     if (plist.n_sites, plist.n_cross) != (n_sites, n_cross):
         raise ValueError(f"a pair list for n_sites {plist.n_sites}, n_cross {plist.n_cross} with xyz {shapes[0]}"
                          + ("" if cross_xyz is None else f" and cross_xyz {shapes[1]}"))
+    if box is not None:
+        box = _as_box(box, shapes[0][0])
     if _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
         from ._autograd import PairListDist
 
         K.lib()
-        return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square))
+        if box is None:
+            return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square))
+        return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square),
+                                  box.to(xyz.device))
     xyz = xyz if isinstance(xyz, torch.Tensor) else torch.as_tensor(np.asarray(xyz))
     if cross_xyz is None:
         other = xyz
@@ -228,7 +317,38 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False) -> torch.Te
     i = torch.from_numpy(plist.pairs[:, 0].copy()).to(other.device)
     j = torch.from_numpy(plist.pairs[:, 1].copy()).to(xyz.device)
     disp = xyz[:, j] - other[:, i]
+    if box is not None:
+        disp = _wrap(disp, box)
     return (disp**2).sum(dim=-1) if square else torch.linalg.vector_norm(disp, dim=-1)
+
+
+def min_distances(xyz, cross_xyz=None, square: bool = False, box=None) -> torch.Tensor:
+    """The smallest distance each pair of sites reaches over the trajectory: (other_n_sites, n_sites),
+    ``out[i, j] = min_t |xyz[t, j] - (cross_xyz if given else xyz)[t, i]|`` (squared with ``square``; the minimum
+    image under ``box``, as in ``pair_distances``).  Detached: it is the input of a list builder
+    (``PairList.from_cutoff``), not of a loss.  A NaN coordinate makes every pair of its site NaN; without frames
+    every minimum is +inf.
+
+    float32/float64 GPU tensors run on K9e (``aggf_pair_min``), which reads the coordinates alone: nothing of the size
+    (n_steps, other, self) is formed.  Everything else is ``amin`` over plain torch."""
+    for a in (xyz,) if cross_xyz is None else (xyz, cross_xyz):
+        shape = tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+        if len(shape) != 3 or shape[2] != 3:
+            raise ValueError(f"sites must have shape (n_steps, n_sites, 3); got {shape}")
+    n_steps = int(xyz.shape[0]) if hasattr(xyz, "shape") else len(xyz)
+    if box is not None:
+        box = _as_box(box, n_steps)
+    if _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
+        x = xyz.detach()
+        c = x if cross_xyz is None else cross_xyz.detach()
+        ct = torch.promote_types(x.dtype, c.dtype)
+        x, c = x.to(ct).contiguous(), c.to(ct).contiguous()
+        return K.pair_min(x, c, bool(square), None if box is None else box.to(device=x.device, dtype=ct).contiguous())
+    with torch.no_grad():
+        d = _distances(xyz, cross_xyz, True, False, square, box)
+        if d.shape[0] == 0:
+            return torch.full(tuple(d.shape[1:]), float("inf"), dtype=d.dtype, device=d.device)
+        return d.amin(dim=0)
 
 
 def distances(
@@ -240,14 +360,39 @@ def distances(
 ) -> torch.Tensor:
     """Differentiable per-frame distances (reference jaxutil.py:103-187): (n_steps, n_sites, n_sites) matrices, or
     (n_steps, other_n_sites, n_sites) with ``cross_xyz``, or the flattened upper triangles (``return_matrix=False``);
-    displacements (one more trailing axis) with ``return_displacements``; squared distances with ``square``."""
+    displacements (one more trailing axis) with ``return_displacements``; squared distances with ``square``.  The
+    signature is the reference's; under a periodic box use ``distances_in_box``."""
+    return _distances(xyz, cross_xyz, return_matrix, return_displacements, square, None)
+
+
+def distances_in_box(
+    xyz: torch.Tensor,
+    box,
+    cross_xyz: Union[torch.Tensor, None] = None,
+    return_matrix: bool = True,
+    return_displacements: bool = False,
+    square: bool = False,
+) -> torch.Tensor:
+    """``distances`` under an orthorhombic periodic cell (not in the reference): minimum-image distances and
+    displacements for ``box`` as in ``pair_distances``.  On GPU tensors both forms run on the pair-list kernels -- the
+    matrix over ``PairList.all_pairs``, reshaped -- since the matrix kernels K9a / K9b have no box form."""
+    if box is None:
+        raise ValueError("distances_in_box needs a box; without one it is distances")
+    return _distances(xyz, cross_xyz, return_matrix, return_displacements, square, box)
+
+
+def _distances(xyz, cross_xyz, return_matrix, return_displacements, square, box) -> torch.Tensor:
     if cross_xyz is not None and not return_matrix:
         raise ValueError("Cross distances only supported when return_matrix is truthy.")
     if return_displacements and not return_matrix:
         raise ValueError("Displacements only supported when return_matrix is truthy.")
     if not return_displacements and _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
         if not return_matrix:  # the pairs i < j as a list: no (T, n, n) array, forward or backward
-            return pair_distances(xyz, PairList.upper_triangle(xyz.shape[1]), square=square)
+            return pair_distances(xyz, PairList.upper_triangle(xyz.shape[1]), square=square, box=box)
+        if box is not None:
+            n_cross = None if cross_xyz is None else cross_xyz.shape[1]
+            flat = pair_distances(xyz, PairList.all_pairs(xyz.shape[1], n_cross), cross_xyz, square=square, box=box)
+            return flat.reshape(xyz.shape[0], xyz.shape[1] if n_cross is None else n_cross, xyz.shape[1])
         from ._autograd import PairDist
 
         K.lib()
@@ -258,6 +403,8 @@ def distances(
     else:
         cross_xyz = cross_xyz if isinstance(cross_xyz, torch.Tensor) else torch.as_tensor(np.asarray(cross_xyz))
         disp = xyz[:, None, :, :] - cross_xyz[:, :, None, :]
+    if box is not None:
+        disp = _wrap(disp, _as_box(box, xyz.shape[0]))
     if return_displacements:
         return disp
     if square:

@@ -514,6 +514,40 @@ int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void
                         int32_t n, int64_t P, int in_dtype, void* A, void* B, int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K9c / K9d under a periodic box, and K9e (jaxutil.pair_distances with `box`,
+ * jaxutil.distances_in_box, jaxutil.min_distances, PairList.from_cutoff).  Orthorhombic boxes: `box` holds three lengths
+ * per frame, (T, 3) with box_stride 3, or one (3,) for all frames with box_stride 0, on the
+ * device in the operands' dtype.  Every displacement component d of u is replaced by its
+ * minimum image
+ *     k = rint(d * invL),  d' = fma(-k, L, d),   invL = 1 / L   (round to nearest even)
+ * The tangent operands V - Y of DOT are not wrapped.  A length that is not a positive finite
+ * number makes every output of its frame NaN.  Where every |d| is far below L / 2 the results
+ * are those of the open entry points bit for bit.
+ *
+ * aggf_pair_list_dist_pbc / aggf_pair_list_pull_pbc: the arguments, launch plan and guarantees
+ *   of aggf_pair_list_dist / aggf_pair_list_pull, plus the box (NULL or a stride other than 0
+ *   or 3: AGGF_ERR_ARG).
+ * aggf_pair_min (K9e): out[i,j] = min_t |X[t,j] - C[t,i]| (m, n) in `dtype`; square != 0: the
+ *   squared distance.  box NULL: open; else the minimum image as above.  The minimum is taken
+ *   over the squared distances of aggf_pair_dist's arithmetic and rooted once, which gives the
+ *   bits of the minimum of aggf_pair_list_dist's distances.  A NaN distance makes its pair NaN.
+ *   Frames may be split over workgroups, the partial minima going through ws: ws_bytes >= the
+ *   query's value for the same (T, m, n, dtype) (0 when one split suffices; ws may then be
+ *   NULL).  No atomics.  T, m or n zero returns AGGF_OK without a launch and without writing.
+ * ------------------------------------------------------------------------- */
+int aggf_pair_list_dist_pbc(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
+                            int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, const void* box,
+                            int32_t box_stride, void* out, void* stream);
+int aggf_pair_list_pull_pbc(const void* W, const void* Dv, const void* X, const void* C, const int32_t* pairs,
+                            const int32_t* a_ptr, const int32_t* a_idx, const int32_t* b_ptr,
+                            const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m,
+                            int32_t n, int64_t P, int in_dtype, const void* box, int32_t box_stride, void* A,
+                            void* B, int out_dtype, void* stream);
+size_t aggf_pair_min_workspace_bytes(int64_t T, int32_t m, int32_t n, int dtype);
+int aggf_pair_min(const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype, const void* box,
+                  int32_t box_stride, int square, void* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K10  The clipped Gaussian radial basis of qp/jaxfeat.py and its derivatives of any order
  * (the autograd Functions Basis / BasisDot of aggforce_amd/_autograd.py; reference
  * jaxfeat.py:187-567, which JAX differentiates itself).  With z = (r - c_k) / width and

@@ -19,8 +19,15 @@ With --pairlist the rows of the pair-list kernels instead (K9c / K9d, device eve
                in the same process, the two alternating; ``*_matrix_ms_min_max`` = the spread of the matrix route's repeats
   bonded_*     a 256-site chain with its 1-3 and 1-4 neighbours (762 pairs), 1e4 frames
   form_sweep_* K9d's lane-per-site and wave-per-site forms on lists of 2 .. 128 entries per site (PLP_LANE_DEG)
+With --pbc the rows of the periodic-box kernels (device events, median of --reps):
+  pbc_triangle_*  K9c / K9d on the triangle list at (1e4, 256) and (1e5, 64), both dtypes, under a constant box
+               (``box_*_ms``) and a per-frame box (``frames_*_ms``), each beside its open form (``open_*_ms``) measured
+               in the same process, alternating; ``*_box_over_open`` = open time / box time (1 = parity)
+  pairmin_*    K9e at (T, n) = (1e5, 256) and (1e4, 1024), open and under a box: ms and (frame, pair) evaluations per
+               second (T n^2 / time)
 Usage (GPU box): python tools/distgrad_bench.py [--rocprof OUTDIR] > profiles/distgrad_bench.jsonl
                  python tools/distgrad_bench.py --pairlist --parent HASH >> profiles/distgrad_bench.jsonl
+                 python tools/distgrad_bench.py --pbc >> profiles/distgrad_bench.jsonl
 """
 import argparse
 import csv
@@ -288,6 +295,64 @@ def pairlist_rows(args):
         print(json.dumps(form_sweep(10000, 256, dt, args.reps)), flush=True)
 
 
+# ------------------------------------------------------------------ periodic boxes (K9c / K9d box forms, K9e): --pbc
+def alternating_ms(calls, reps):
+    """{name: median ms} of several calls measured in turn, one after the other in every repeat."""
+    for fn in calls.values():
+        fn()
+    times = {k: [] for k in calls}
+    for _ in range(reps):
+        for k, fn in calls.items():
+            times[k].append(event_ms(fn))
+    return {k: round(statistics.median(v), 4) for k, v in times.items()}
+
+
+def pbc_rows(args):
+    import numpy as np
+    import torch
+
+    from aggforce_amd import _kernels as K
+    from aggforce_amd.jaxutil import PairList
+
+    lengths = (9.1, 10.3, 11.7)  # (the lattice of `make` spans about 10: most pairs wrap in some component)
+    for name, T, _, n, dt in CASES:
+        if args.cases and name not in args.cases:
+            continue
+        x, v, _ = make(T, 1, n, dt)
+        tab = PairList(np.stack(np.triu_indices(n, 1), axis=1), n).on("cuda")
+        P = tab.n_pairs
+        w = torch.randn((T, P), device="cuda", dtype=x.dtype)
+        box = torch.tensor(lengths, device="cuda", dtype=x.dtype)
+        boxes = (box[None] * (1 + 0.02 * torch.rand((T, 3), device="cuda", dtype=x.dtype))).contiguous()
+        d = K.pair_list_dist(x, x, tab, box=box)
+        rec = {"case": "pbc_triangle_" + name, "T": T, "n": n, "P": P, "dtype": dt, "timing": "events", "box": lengths}
+        ops = {"list_dist": lambda **k: K.pair_list_dist(x, x, tab, **k),
+               "list_dot": lambda **k: K.pair_list_dist(x, x, tab, K.PAIR_DOT, v, v, **k),
+               "list_pull": lambda **k: K.pair_list_pull(w, x, x, tab, **k),
+               "list_pull_dv": lambda **k: K.pair_list_pull(w, x, x, tab, dv=d, **k)}
+        for op, fn in ops.items():
+            ms = alternating_ms({"open": fn, "box": lambda: fn(box=box), "frames": lambda: fn(box=boxes)}, args.reps)
+            for form, t in ms.items():
+                rec[f"{form}_{op}_ms"] = t
+            rec[f"{op}_box_over_open"] = round(ms["open"] / ms["box"], 3)
+            rec[f"{op}_frames_over_open"] = round(ms["open"] / ms["frames"], 3)
+        print(json.dumps(rec), flush=True)
+        del x, v, w, d, boxes
+        torch.cuda.empty_cache()
+    for T, n in ((100000, 256), (10000, 1024)):
+        for dt in ("f32", "f64"):
+            x, _, _ = make(T, 1, n, dt)
+            box = torch.tensor(lengths if n == 256 else (16.1, 17.3, 18.7), device="cuda", dtype=x.dtype)
+            ms = alternating_ms({"open": lambda: K.pair_min(x, x), "box": lambda: K.pair_min(x, x, box=box)}, args.reps)
+            rec = {"case": f"pairmin_T{T}_n{n}_{dt}", "T": T, "n": n, "dtype": dt, "timing": "events"}
+            for form, t in ms.items():
+                rec[f"{form}_ms"] = t
+                rec[f"{form}_evals_per_s"] = float(f"{T * n * n / (t * 1e-3):.4g}")
+            print(json.dumps(rec), flush=True)
+            del x
+            torch.cuda.empty_cache()
+
+
 def child(args):
     """One dispatch of every op, --reps times, cases and ops in order (the rocprofv3 run)."""
     import torch
@@ -350,6 +415,7 @@ def main():
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--pairlist", action="store_true", help="the K9c / K9d rows instead (device events)")
+    ap.add_argument("--pbc", action="store_true", help="the periodic-box rows instead (K9c / K9d box forms, K9e)")
     ap.add_argument("--parent", default="", help="8-character hash of the commit whose triangle route is compared")
     args = ap.parse_args()
     if args.child:
@@ -357,6 +423,9 @@ def main():
         return
     if args.pairlist:
         pairlist_rows(args)
+        return
+    if args.pbc:
+        pbc_rows(args)
         return
     import torch
 
