@@ -996,30 +996,43 @@ def feat_weights(feat: torch.Tensor, coef: torch.Tensor, out: torch.Tensor, site
 # ------------------------------------------------------------------ K6 pair-distance variance
 
 
-def pair_dist_var(x: torch.Tensor) -> torch.Tensor:
-    """(N, N) float64 population variance over frames of every pair distance; see aggf_pair_dist_var."""
+def pair_dist_var(x: torch.Tensor, box: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(N, N) float64 population variance over frames of every pair distance; see aggf_pair_dist_var.  ``box`` ((3,)
+    or (T, 3), x's dtype and device): the distances are those of the minimum image under that orthorhombic box
+    (aggf_pair_dist_var_pbc); a frame whose box is bad makes every off-diagonal element NaN."""
     l = lib()
     T, N, _ = x.shape
+    stride = None if box is None else _box_arg("pair_dist_var", box, x)
     var = torch.empty((N, N), dtype=torch.float64, device=x.device)
     need = l.aggf_pair_dist_var_workspace_bytes(T, N)
     ws = workspace(need, x.device, "pairs")
     with _timed("pair_var"):
-        check(l.aggf_pair_dist_var(ptr(x), T, N, dtype_code(x.dtype), ptr(var), ptr(ws), need, stream_ptr()),
-              "aggf_pair_dist_var")
+        if box is None:
+            check(l.aggf_pair_dist_var(ptr(x), T, N, dtype_code(x.dtype), ptr(var), ptr(ws), need, stream_ptr()),
+                  "aggf_pair_dist_var")
+        else:
+            check(l.aggf_pair_dist_var_pbc(ptr(x), T, N, dtype_code(x.dtype), ptr(box), stride, ptr(var), ptr(ws), need,
+                                           stream_ptr()), "aggf_pair_dist_var_pbc")
     return var
 
 
-def pair_dist_moments(x: torch.Tensor):
-    """(mean, var) (N, N) float64 of every pair distance over the frames; see aggf_pair_dist_moments."""
+def pair_dist_moments(x: torch.Tensor, box: Optional[torch.Tensor] = None):
+    """(mean, var) (N, N) float64 of every pair distance over the frames; see aggf_pair_dist_moments.  ``box``: as
+    ``pair_dist_var`` (aggf_pair_dist_moments_pbc)."""
     l = lib()
     T, N, _ = x.shape
+    stride = None if box is None else _box_arg("pair_dist_moments", box, x)
     mean = torch.empty((N, N), dtype=torch.float64, device=x.device)
     var = torch.empty((N, N), dtype=torch.float64, device=x.device)
     need = l.aggf_pair_dist_var_workspace_bytes(T, N)
     ws = workspace(need, x.device, "pairs")
     with _timed("pair_var"):
-        check(l.aggf_pair_dist_moments(ptr(x), T, N, dtype_code(x.dtype), ptr(mean), ptr(var), ptr(ws), need, stream_ptr()),
-              "aggf_pair_dist_moments")
+        if box is None:
+            check(l.aggf_pair_dist_moments(ptr(x), T, N, dtype_code(x.dtype), ptr(mean), ptr(var), ptr(ws), need,
+                                           stream_ptr()), "aggf_pair_dist_moments")
+        else:
+            check(l.aggf_pair_dist_moments_pbc(ptr(x), T, N, dtype_code(x.dtype), ptr(box), stride, ptr(mean), ptr(var),
+                                               ptr(ws), need, stream_ptr()), "aggf_pair_dist_moments_pbc")
     return mean, var
 
 

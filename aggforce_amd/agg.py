@@ -64,12 +64,21 @@ def _mean_square(sumsq, count: int, comm=None) -> float:
     return float(s / n) if n else float("nan")
 
 
+def _checked_box(box, n_steps: int):
+    """``box`` as ``jaxutil._as_box`` normalises it: shape (3,) or (n_steps, 3) (ValueError otherwise), host values
+    checked, no device work."""
+    from .jaxutil import _as_box
+
+    return _as_box(box, int(n_steps))
+
+
 def project_forces(
     coords,
     forces,
     coord_map: LinearMap,
     constrained_inds: Union[Constraints, str, None] = PROJECT_FORCES_CNSTR_AUTO,
     method: Callable[..., TMap] = qp_linear_map,
+    box=None,
     **kwargs,
 ) -> Dict[str, Any]:
     """Produce an optimised force map and the mapped trajectory (reference agg.py:49-136).
@@ -81,6 +90,14 @@ def project_forces(
     A ``comm=`` keyword (torch.distributed group over which the frames are sharded) is
     forwarded to ``method`` and also used to reduce the residual.
 
+    ``box`` (extra; not forwarded to ``method``): the lengths of an orthorhombic periodic cell, (3,) or
+    (n_steps, 3), for coordinates that are wrapped into it.  It is used by the "auto" guess alone, which then
+    measures minimum-image distances (``guess_pairwise_constraints(..., box=)``) and so keeps the rigid pairs
+    that straddle a face of the cell in some frames; with explicit constraints or None its shape is checked and
+    it is otherwise ignored.  It changes nothing else: mapped coordinates are still ``coord_map`` applied to
+    the coordinates as given -- exact for slice maps, and the caller's business for averaging maps of molecules
+    that the wrap has split (unwrap those first) -- and featurisers (``gb_feat``) still see open distances.
+
     Returns a dict with keys mapped_coords, mapped_forces, tmap, residual, constraints.
     """
     if isinstance(constrained_inds, str) and constrained_inds == PROJECT_FORCES_CNSTR_AUTO:
@@ -89,7 +106,9 @@ def project_forces(
                 f"If constrained_inds is {PROJECT_FORCES_CNSTR_AUTO}, coords cannot be None."
             )
         # (with comm= the per-rank distance statistics are pooled exactly: every rank gets the same set)
-        constrained_inds = guess_pairwise_constraints(coords, comm=kwargs.get("comm"))
+        constrained_inds = guess_pairwise_constraints(coords, comm=kwargs.get("comm"), box=box)
+    elif box is not None:
+        _checked_box(box, forces.shape[0])
     with K.upload_cache():
         t = Trajectory(coords=coords, forces=forces)
         fused_ss = None  # sum of squares of the mapped forces when the apply kernel accumulated it
@@ -291,6 +310,7 @@ def project_forces_grid_cv(
     reuse_gram: bool = True,
     method_rng=None,
     cv_noise=None,
+    box=None,
     **kwargs,
 ) -> Dict[str, Dict[NamedTuple, T]]:
     """Grid cross-validation over project_forces arguments (reference agg.py:142-235).
@@ -312,8 +332,15 @@ def project_forces_grid_cv(
 
     (The reference calls ``trained_tmap.from_arrays`` at agg.py:224, which no TMap defines; the
     intended ``map_arrays`` is used here.)
+
+    ``box`` (extra): as in ``project_forces``, for all ``n_frames`` frames.  The loop hands every training
+    subset its box -- a (3,) box as it is, a per-frame box indexed with the training frames -- for the "auto"
+    guess.  The one-pass forms take explicit constraints, so the box has no effect on them and does not keep a
+    call from them.
     """
     n_frames = forces.shape[0]
+    if box is not None:
+        box = _checked_box(box, n_frames)
     frames = np.arange(n_frames)
     (np.random.default_rng() if rng is None else rng).shuffle(frames)
     folds = np.array_split(frames, n_folds)
@@ -351,6 +378,8 @@ def project_forces_grid_cv(
             return done
     results: Dict[str, Dict[Any, Any]] = {SCORES_KNAME: {}, SDS_KNAME: {}, NRUNS_KNAME: {}}
     take = _take_frames
+    if box is not None:
+        import torch
     for label, args in grid:
         scores = []
         merged = dict(kwargs, **args)
@@ -358,6 +387,8 @@ def project_forces_grid_cv(
             merged["rng"] = method_rng
         for k, val_idx in enumerate(folds):
             train_idx = np.concatenate([f for j, f in enumerate(folds) if j != k])
+            if box is not None:
+                merged["box"] = box if box.dim() == 1 else box[torch.as_tensor(train_idx, device=box.device)]
             try:
                 tmap = project_forces(coords=take(coords, train_idx), forces=take(forces, train_idx), **merged)[
                     TMAP_KNAME

@@ -8,6 +8,14 @@
 // One workgroup = one 64x64 tile of pairs x one frame range; thread = 4x4 pairs in registers;
 // 8 frames of the two 64-atom position blocks are staged in LDS per barrier.  Partial sums per
 // frame range go to slabs and are combined in a fixed order (deterministic).
+//
+// pair_stats_pbc_kernel / pair_var_pbc_kernel: the same two under an orthorhombic box per frame (`box` (T, 3) with
+// bstride 3, or (3,) with bstride 0, in the coordinates' dtype and widened as they are): every displacement component
+// is replaced by its minimum image in float64 (min_image, aggf_common.h), d_0 included -- the minimum-image distance
+// of frame 0 under frame 0's box.  L and 1/L of the 8 staged frames are formed once per stage (box_lengths) and kept
+// in LDS beside the positions.  A frame whose box is bad is NaN, and with it every off-diagonal variance (the
+// diagonal stays 0).  Each pair of kernels shares one __device__ body; the open ones keep their names, arguments and
+// bits, and both forms share the plan, the slabs and the reduction order.
 #include "aggf_common.h"
 
 namespace aggf {
@@ -15,12 +23,28 @@ namespace aggf {
 constexpr int PT = 64;   // pair tile edge
 constexpr int PFB = 8;   // frames per LDS stage
 
+// The roundings of K6, written out for the reason pair_dot3's are: left to the compiler's contraction, the 16 pairs of
+// a thread do not all get the same fused form, and the two threads that hold (i, j) and (j, i) of a diagonal tile --
+// or the open and the box kernel -- then differ in the last bit.  |u| = sqrt(fma(uz, uz, fma(ux, ux, uy uy))), the
+// shifted sums s1 += dd, s2 = fma(dd, dd, s2), and var = fma(-m, m, q / T): the forms these kernels have always had.
+__device__ __forceinline__ double pair_norm(double ux, double uy, double uz) {
+  return sqrt(pair_dot3(ux, ux, uy, uy, uz, uz));
+}
+
+// the three widened lengths of one frame's box, and their inverses (box_lengths in float64)
 template <typename TIn>
-__global__ __launch_bounds__(256) void pair_stats_kernel(const TIn* __restrict__ X, int64_t T, int32_t N,
-                                                         int32_t nt1, int32_t n_tiles,
-                                                         int64_t frames_per_split,
-                                                         double* __restrict__ slabs) {
-  __shared__ double sp[2][PFB][PT][3];  // [i-block | j-block][frame][atom][xyz]
+__device__ __forceinline__ bool box_lengths_wide(const TIn* __restrict__ box, double L[3], double invL[3]) {
+  const double b[3] = {(double)box[0], (double)box[1], (double)box[2]};
+  return box_lengths(b, L, invL);
+}
+
+template <typename TIn, bool PBC>
+__device__ __forceinline__ void pair_stats_body(const TIn* __restrict__ X, int64_t T, int32_t N, int32_t nt1,
+                                                int32_t n_tiles, int64_t frames_per_split,
+                                                const TIn* __restrict__ box, int32_t bstride,
+                                                double* __restrict__ slabs) {
+  __shared__ double sp[2][PFB][PT][3];    // [i-block | j-block][frame][atom][xyz]
+  __shared__ double sb[PBC ? PFB : 1][6];  // PBC: [frame][L xyz | 1/L xyz]
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
   const int ks = b / n_tiles;
@@ -56,10 +80,13 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const TIn* __restrict__
     double pi[4][3], pj[4][3];
     for (int x = 0; x < 4; ++x) load_atom(0, ti * PT + bi + x, pi[x]);
     for (int y = 0; y < 4; ++y) load_atom(0, tj * PT + bj + y, pj[y]);
+    double L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
+    if (PBC) box_lengths_wide(box, L, iL);  // frame 0's box
     for (int x = 0; x < 4; ++x)
       for (int y = 0; y < 4; ++y) {
-        const double dx = pj[y][0] - pi[x][0], dy = pj[y][1] - pi[x][1], dz = pj[y][2] - pi[x][2];
-        d0[x][y] = sqrt(dx * dx + dy * dy + dz * dz);
+        double dx = pj[y][0] - pi[x][0], dy = pj[y][1] - pi[x][1], dz = pj[y][2] - pi[x][2];
+        if (PBC) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+        d0[x][y] = pair_norm(dx, dy, dz);
       }
   }
   double s1[4][4], s2[4][4];
@@ -77,18 +104,28 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const TIn* __restrict__
       if (t < t_end && a < N) v = (double)X[(t * N + a) * 3 + q % 3];
       (&sp[side][f][0][0])[q] = v;
     }
+    if (PBC && tid < PFB) {  // (frames past t_end are staged but never read)
+      const int64_t t = t0 + tid;
+      if (t < t_end) box_lengths_wide(box + t * bstride, &sb[tid][0], &sb[tid][3]);
+    }
     __syncthreads();
     const int nf = (int)((t_end - t0) < PFB ? (t_end - t0) : PFB);
     for (int f = 0; f < nf; ++f) {
+      double L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
+      if (PBC) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) L[k] = sb[f][k], iL[k] = sb[f][3 + k];
+      }
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
         const double ax = sp[0][f][bi + x][0], ay = sp[0][f][bi + x][1], az = sp[0][f][bi + x][2];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
-          const double dx = sp[1][f][bj + y][0] - ax, dy = sp[1][f][bj + y][1] - ay, dz = sp[1][f][bj + y][2] - az;
-          const double dd = sqrt(dx * dx + dy * dy + dz * dz) - d0[x][y];
+          double dx = sp[1][f][bj + y][0] - ax, dy = sp[1][f][bj + y][1] - ay, dz = sp[1][f][bj + y][2] - az;
+          if (PBC) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+          const double dd = pair_norm(dx, dy, dz) - d0[x][y];
           s1[x][y] += dd;
-          s2[x][y] += dd * dd;
+          s2[x][y] = __builtin_fma(dd, dd, s2[x][y]);
         }
       }
     }
@@ -102,13 +139,31 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const TIn* __restrict__
     }
 }
 
-// var[i,j] (N x N, symmetric, diagonal 0) from the slabs, fixed summation order
-// mean (optional): mean distance over the frames = d0 + shifted mean, d0 recomputed from frame 0 of X
 template <typename TIn>
-__global__ __launch_bounds__(256) void pair_var_kernel(const double* __restrict__ slabs, int32_t nt1,
-                                                       int32_t ksplit, int32_t N, int64_t T,
-                                                       double* __restrict__ var, const TIn* __restrict__ X,
-                                                       double* __restrict__ mean) {
+__global__ __launch_bounds__(256) void pair_stats_kernel(const TIn* __restrict__ X, int64_t T, int32_t N,
+                                                         int32_t nt1, int32_t n_tiles,
+                                                         int64_t frames_per_split,
+                                                         double* __restrict__ slabs) {
+  pair_stats_body<TIn, false>(X, T, N, nt1, n_tiles, frames_per_split, nullptr, 0, slabs);
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void pair_stats_pbc_kernel(const TIn* __restrict__ X, int64_t T, int32_t N,
+                                                             int32_t nt1, int32_t n_tiles,
+                                                             int64_t frames_per_split,
+                                                             const TIn* __restrict__ box, int32_t bstride,
+                                                             double* __restrict__ slabs) {
+  pair_stats_body<TIn, true>(X, T, N, nt1, n_tiles, frames_per_split, box, bstride, slabs);
+}
+
+// var[i,j] (N x N, symmetric, diagonal 0) from the slabs, fixed summation order
+// mean (optional): mean distance over the frames = d0 + shifted mean, d0 recomputed from frame 0 of X (PBC: its
+// minimum image under frame 0's box, as the statistics kernel formed it)
+template <typename TIn, bool PBC>
+__device__ __forceinline__ void pair_var_body(const double* __restrict__ slabs, int32_t nt1, int32_t ksplit,
+                                              int32_t N, int64_t T, double* __restrict__ var,
+                                              const TIn* __restrict__ X, const TIn* __restrict__ box,
+                                              double* __restrict__ mean) {
   int tile = blockIdx.x;
   const int tile_lin = tile;
   int ti = 0;
@@ -122,6 +177,8 @@ __global__ __launch_bounds__(256) void pair_var_kernel(const double* __restrict_
   }
   const int tj = ti + tile;
   const double* base = slabs + (int64_t)tile_lin * ksplit * (2 * PT * PT);
+  double L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
+  if (PBC && mean) box_lengths_wide(box, L, iL);  // frame 0's box
   for (int e = threadIdx.x; e < PT * PT; e += 256) {
     const int i = ti * PT + e / PT, j = tj * PT + e % PT;
     if (i >= N || j >= N) continue;
@@ -131,20 +188,40 @@ __global__ __launch_bounds__(256) void pair_var_kernel(const double* __restrict_
       q += base[(int64_t)ks * (2 * PT * PT) + PT * PT + e];
     }
     const double m = a / (double)T;
-    double v = q / (double)T - m * m;
+    double v = __builtin_fma(-m, m, q / (double)T);
     if (v < 0.0) v = 0.0;
     if (i == j) v = 0.0;
     var[(int64_t)i * N + j] = v;
     var[(int64_t)j * N + i] = v;
     if (mean) {
-      const double dx = (double)X[(int64_t)j * 3 + 0] - (double)X[(int64_t)i * 3 + 0],
-                   dy = (double)X[(int64_t)j * 3 + 1] - (double)X[(int64_t)i * 3 + 1],
-                   dz = (double)X[(int64_t)j * 3 + 2] - (double)X[(int64_t)i * 3 + 2];
-      const double mu = i == j ? 0.0 : sqrt(dx * dx + dy * dy + dz * dz) + m;
+      double dx = (double)X[(int64_t)j * 3 + 0] - (double)X[(int64_t)i * 3 + 0],
+             dy = (double)X[(int64_t)j * 3 + 1] - (double)X[(int64_t)i * 3 + 1],
+             dz = (double)X[(int64_t)j * 3 + 2] - (double)X[(int64_t)i * 3 + 2];
+      if (PBC) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+      // (from float64 coordinates the inner product here is ux ux and uy uy the fused one: the form this
+      // instantiation has always had)
+      const double mu = i == j ? 0.0 : (sizeof(TIn) == 8 ? pair_norm(dy, dx, dz) : pair_norm(dx, dy, dz)) + m;
       mean[(int64_t)i * N + j] = mu;
       mean[(int64_t)j * N + i] = mu;
     }
   }
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void pair_var_kernel(const double* __restrict__ slabs, int32_t nt1,
+                                                       int32_t ksplit, int32_t N, int64_t T,
+                                                       double* __restrict__ var, const TIn* __restrict__ X,
+                                                       double* __restrict__ mean) {
+  pair_var_body<TIn, false>(slabs, nt1, ksplit, N, T, var, X, nullptr, mean);
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void pair_var_pbc_kernel(const double* __restrict__ slabs, int32_t nt1,
+                                                           int32_t ksplit, int32_t N, int64_t T,
+                                                           double* __restrict__ var, const TIn* __restrict__ X,
+                                                           const TIn* __restrict__ box,
+                                                           double* __restrict__ mean) {
+  pair_var_body<TIn, true>(slabs, nt1, ksplit, N, T, var, X, box, mean);
 }
 
 // out = weight * (var_r + (mean_r - mean)^2): this rank's term of the pooled variance
@@ -182,8 +259,30 @@ extern "C" size_t aggf_pair_dist_var_workspace_bytes(int64_t T, int32_t N) {
   return (size_t)n_tiles * ksplit * 2 * PT * PT * sizeof(double) + 256;
 }
 
-static int pair_moments_impl(const void* X, int64_t T, int32_t N, int dtype, double* mean, double* var, void* ws,
-                             size_t ws_bytes, void* stream_v, const char* who) {
+// one dtype's two launches: box NULL, the open kernels with the arguments they have always had; else the box forms
+template <typename TIn>
+static int launch_pair_moments(dim3 grid, hipStream_t stream, const void* X, int64_t T, int32_t N, int nt1,
+                               int n_tiles, int ksplit, int64_t fps, const void* box, int32_t bstride, double* slabs,
+                               double* mean, double* var) {
+  if (box) {
+    AGGF_LAUNCH(pair_stats_pbc_kernel<TIn>, grid, dim3(256), 0, stream, (const TIn*)X, T, N, nt1, n_tiles, fps,
+                (const TIn*)box, bstride, slabs);
+    AGGF_LAUNCH_OK();
+    AGGF_LAUNCH(pair_var_pbc_kernel<TIn>, dim3(n_tiles), dim3(256), 0, stream, slabs, nt1, ksplit, N, T, var,
+                (const TIn*)X, (const TIn*)box, mean);
+  } else {
+    AGGF_LAUNCH(pair_stats_kernel<TIn>, grid, dim3(256), 0, stream, (const TIn*)X, T, N, nt1, n_tiles, fps, slabs);
+    AGGF_LAUNCH_OK();
+    AGGF_LAUNCH(pair_var_kernel<TIn>, dim3(n_tiles), dim3(256), 0, stream, slabs, nt1, ksplit, N, T, var,
+                (const TIn*)X, mean);
+  }
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+// K6, open (box NULL) or under a box: one plan, one workspace layout for both
+static int pair_moments_impl(const void* X, int64_t T, int32_t N, int dtype, const void* box, int32_t bstride,
+                             double* mean, double* var, void* ws, size_t ws_bytes, void* stream_v, const char* who) {
   hipStream_t stream = (hipStream_t)stream_v;
   if (!X || !var || !ws) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
   if (T <= 0 || N <= 0) return fail(AGGF_ERR_ARG, "%s: empty problem", who);
@@ -194,32 +293,47 @@ static int pair_moments_impl(const void* X, int64_t T, int32_t N, int dtype, dou
     return fail(AGGF_ERR_WORKSPACE, "%s: workspace too small", who);
   double* slabs = reinterpret_cast<double*>(ws);
   const dim3 grid((unsigned)((int64_t)n_tiles * ksplit));
-  if (dtype == AGGF_F64) {
-    AGGF_LAUNCH(pair_stats_kernel<double>, grid, dim3(256), 0, stream, (const double*)X, T, N, nt1, n_tiles, fps, slabs);
-    AGGF_LAUNCH_OK();
-    AGGF_LAUNCH(pair_var_kernel<double>, dim3(n_tiles), dim3(256), 0, stream, slabs, nt1, ksplit, N, T, var,
-                       (const double*)X, mean);
-  } else if (dtype == AGGF_F32) {
-    AGGF_LAUNCH(pair_stats_kernel<float>, grid, dim3(256), 0, stream, (const float*)X, T, N, nt1, n_tiles, fps, slabs);
-    AGGF_LAUNCH_OK();
-    AGGF_LAUNCH(pair_var_kernel<float>, dim3(n_tiles), dim3(256), 0, stream, slabs, nt1, ksplit, N, T, var,
-                       (const float*)X, mean);
-  } else {
-    return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
-  }
-  AGGF_LAUNCH_OK();
+  if (dtype == AGGF_F64)
+    return launch_pair_moments<double>(grid, stream, X, T, N, nt1, n_tiles, ksplit, fps, box, bstride, slabs, mean, var);
+  if (dtype == AGGF_F32)
+    return launch_pair_moments<float>(grid, stream, X, T, N, nt1, n_tiles, ksplit, fps, box, bstride, slabs, mean, var);
+  return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
+}
+
+// the box of a box form: (T, 3) or (3,) in the coordinates' dtype
+static int pair_moments_box(const char* who, const void* box, int32_t box_stride) {
+  if (!box) return fail(AGGF_ERR_ARG, "%s: NULL box", who);
+  if (box_stride != 0 && box_stride != 3) return fail(AGGF_ERR_ARG, "%s: box_stride %d is neither 0 nor 3", who, box_stride);
   return AGGF_OK;
 }
 
 extern "C" int aggf_pair_dist_var(const void* X, int64_t T, int32_t N, int dtype, double* var, void* ws,
                                   size_t ws_bytes, void* stream_v) {
-  return pair_moments_impl(X, T, N, dtype, nullptr, var, ws, ws_bytes, stream_v, "aggf_pair_dist_var");
+  return pair_moments_impl(X, T, N, dtype, nullptr, 0, nullptr, var, ws, ws_bytes, stream_v, "aggf_pair_dist_var");
 }
 
 extern "C" int aggf_pair_dist_moments(const void* X, int64_t T, int32_t N, int dtype, double* mean, double* var,
                                       void* ws, size_t ws_bytes, void* stream_v) {
   if (!mean) return fail(AGGF_ERR_ARG, "aggf_pair_dist_moments: NULL pointer");
-  return pair_moments_impl(X, T, N, dtype, mean, var, ws, ws_bytes, stream_v, "aggf_pair_dist_moments");
+  return pair_moments_impl(X, T, N, dtype, nullptr, 0, mean, var, ws, ws_bytes, stream_v, "aggf_pair_dist_moments");
+}
+
+extern "C" int aggf_pair_dist_var_pbc(const void* X, int64_t T, int32_t N, int dtype, const void* box,
+                                      int32_t box_stride, double* var, void* ws, size_t ws_bytes, void* stream_v) {
+  const int rc = pair_moments_box("aggf_pair_dist_var_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return pair_moments_impl(X, T, N, dtype, box, box_stride, nullptr, var, ws, ws_bytes, stream_v,
+                           "aggf_pair_dist_var_pbc");
+}
+
+extern "C" int aggf_pair_dist_moments_pbc(const void* X, int64_t T, int32_t N, int dtype, const void* box,
+                                          int32_t box_stride, double* mean, double* var, void* ws, size_t ws_bytes,
+                                          void* stream_v) {
+  const int rc = pair_moments_box("aggf_pair_dist_moments_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  if (!mean) return fail(AGGF_ERR_ARG, "aggf_pair_dist_moments_pbc: NULL pointer");
+  return pair_moments_impl(X, T, N, dtype, box, box_stride, mean, var, ws, ws_bytes, stream_v,
+                           "aggf_pair_dist_moments_pbc");
 }
 
 extern "C" int aggf_pair_pool_term(const double* var_r, const double* mean_r, const double* mean, double weight,

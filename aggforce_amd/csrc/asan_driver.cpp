@@ -140,6 +140,20 @@ int main() {
   REFUSED(aggf_feat_weights(nullptr, 0, 10, 5, 7, d, 10, d, nullptr));
   REFUSED(aggf_pair_dist_var(nullptr, 10, 5, 1, d, ws, WS, nullptr));
   REFUSED(aggf_pair_dist_moments(p, 10, 5, 1, nullptr, d, ws, WS, nullptr));
+  // K6 box forms: the box's own refusals (NULL, a stride other than 0 or 3), then those of the open twins
+  REFUSED(aggf_pair_dist_var_pbc(p, 10, 5, 1, nullptr, 3, d, ws, WS, nullptr));  // no box
+  REFUSED(aggf_pair_dist_var_pbc(p, 10, 5, 1, p, 1, d, ws, WS, nullptr));        // stride
+  REFUSED(aggf_pair_dist_var_pbc(p, 10, 5, 1, p, -3, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_dist_var_pbc(nullptr, 10, 5, 1, p, 3, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_dist_var_pbc(p, 10, 5, 1, p, 3, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_pair_dist_var_pbc(p, 10, 5, 1, p, 0, d, nullptr, WS, nullptr));
+  REFUSED(aggf_pair_dist_var_pbc(p, 0, 5, 1, p, 3, d, ws, WS, nullptr));
+  REFUSED(aggf_pair_dist_var_pbc(p, 10, 5, 2, p, 3, d, ws, WS, nullptr));        // dtype
+  REFUSED(aggf_pair_dist_var_pbc(p, 1000, 4096, 1, p, 3, d, ws, 1024, nullptr));  // workspace too small
+  REFUSED(aggf_pair_dist_moments_pbc(p, 10, 5, 1, nullptr, 0, d, d + 4096, ws, WS, nullptr));  // no box
+  REFUSED(aggf_pair_dist_moments_pbc(p, 10, 5, 1, p, 2, d, d + 4096, ws, WS, nullptr));        // stride
+  REFUSED(aggf_pair_dist_moments_pbc(p, 10, 5, 1, p, 3, nullptr, d, ws, WS, nullptr));         // no mean
+  REFUSED(aggf_pair_dist_moments_pbc(p, 10, 0, 0, p, 0, d, d + 4096, ws, WS, nullptr));
   // K7: NULL pointers, bad shapes / dtypes / sample counts, widths that are not positive, short workspaces
   REFUSED(aggf_gauss_pair_forces(nullptr, 10, 5, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
   REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, nullptr, ws, WS, nullptr));  // neither G nor E
@@ -222,6 +236,11 @@ int main() {
     RUNS(aggf_augment_concat(p, p, 1, p, p, p, 0, s.T, s.N, s.n_cg, 0.6955215, (char*)p + 4096, (char*)p + 8192, nullptr));
     const size_t wp = aggf_pair_dist_var_workspace_bytes(s.T, s.N);
     if (wp <= WS) RUNS(aggf_pair_dist_var(p, s.T, s.N, 1, d, ws, wp, nullptr));
+    for (int in = 0; in < 2; ++in)
+      for (int32_t bs : {0, 3}) {
+        if (wp <= WS) RUNS(aggf_pair_dist_var_pbc(p, s.T, s.N, in, p, bs, d, ws, wp, nullptr));
+        if (wp <= WS) RUNS(aggf_pair_dist_moments_pbc(p, s.T, s.N, in, p, bs, d, d + 4096, ws, wp, nullptr));
+      }
     RUNS(aggf_synth_normal(p, s.T, s.N, 1, 42100, 5, 0.0, 30.0, 1.5, nullptr));
   }
   {

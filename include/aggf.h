@@ -658,6 +658,23 @@ int aggf_pair_dist_var(const void* X, int64_t T, int32_t N, int dtype, double* v
  * as aggf_pair_dist_var. */
 int aggf_pair_dist_moments(const void* X, int64_t T, int32_t N, int dtype, double* mean, double* var,
                            void* ws, size_t ws_bytes, void* stream);
+/* The same two under a periodic box (aggforce_amd.guess_pairwise_constraints(..., box=), and through it
+ * project_forces(..., box=)): every distance is that of the minimum image under an orthorhombic box, so
+ * a rigid pair that a wrapped trajectory splits across a face keeps its zero variance.  `box`
+ * as in the K9c / K9d box forms: three lengths per frame, (T, 3) with box_stride 3, or one (3,) for all
+ * frames with box_stride 0, on the device in `dtype` (NULL or another stride: AGGF_ERR_ARG).  Coordinates
+ * and lengths are widened to float64 and every displacement component d is replaced by
+ *     k = rint(d * invL),  d' = fma(-k, L, d),   invL = 1 / L   (float64, round to nearest even)
+ * the shift d0 of the sums included: it is the minimum-image distance of frame 0 under frame 0's box.
+ * A length that is not a positive finite number makes its frame NaN, and with it every off-diagonal
+ * element of var (and mean); the diagonal stays 0.  Plan, workspace (aggf_pair_dist_var_workspace_bytes),
+ * summation order and symmetry are those of the open entry points; where every |d| is far below L / 2
+ * the results are theirs bit for bit. */
+int aggf_pair_dist_var_pbc(const void* X, int64_t T, int32_t N, int dtype, const void* box,
+                           int32_t box_stride, double* var, void* ws, size_t ws_bytes, void* stream);
+int aggf_pair_dist_moments_pbc(const void* X, int64_t T, int32_t N, int dtype, const void* box,
+                               int32_t box_stride, double* mean, double* var, void* ws, size_t ws_bytes,
+                               void* stream);
 /* out[e] = weight * (var_r[e] + (mean_r[e] - mean[e])^2) on n float64 elements: one rank's term of the
  * pooled variance above (weight = n_r / n; out may alias var_r). */
 int aggf_pair_pool_term(const double* var_r, const double* mean_r, const double* mean, double weight,

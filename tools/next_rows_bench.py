@@ -2,7 +2,8 @@
 
   cv      project_forces_grid_cv, 5 folds x 4 l2 values: one-pass Gram reuse vs the reference-style loop
   staged  stagedjoptgauss_map fit + application at the C5 size
-  k6      guess_pairwise_constraints' pair-distance statistics kernel
+  k6      guess_pairwise_constraints' pair-distance statistics kernel, and its box form against it (one box, a box
+          per frame): the k6_box row, kept in profiles/k6_box_bench.jsonl
   stream  out-of-core project_forces_streamed from memory-mapped .npy files
 """
 import json
@@ -106,6 +107,38 @@ def bench_k6():
         dt = sync() - t0
     emit(row="k6", workload=f"pair-distance variance, {T} frames x {N} atoms", seconds=dt,
          pair_distances_per_s=T * N * (N - 1) / 2 / dt)
+    del x
+    bench_k6_box(T, N)
+
+
+def bench_k6_box(T, N, calls=10, windows=5):
+    """The open call, one box and a box per frame on the same float64 coordinates (wrapped into the cell), in one
+    process: device events around ``calls`` calls, the three forms taken in turn, median of ``windows`` windows."""
+    side = 1.5 * round(N ** (1 / 3))  # the cell of the lattice the sites jitter around
+    x = K.synth_normal(T, N, torch.float64, 5, sigma=0.3, lattice=1.5)
+    one = torch.full((3,), side, dtype=torch.float64, device=x.device)
+    per_frame = (side * (1 + 0.03 * (2 * torch.rand(T, 3, dtype=torch.float64, device=x.device) - 1))).contiguous()
+    x = (x - per_frame[:, None, :] * torch.floor(x / per_frame[:, None, :])).contiguous()
+    forms = {"open": None, "box": one, "box_per_frame": per_frame}
+    times = {name: [] for name in forms}
+    for name, box in forms.items():  # warm-up: code objects, the workspace
+        K.pair_dist_var(x, box=box)
+    torch.cuda.synchronize()
+    for _ in range(windows):
+        for name, box in forms.items():
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(calls):
+                K.pair_dist_var(x, box=box)
+            stop.record()
+            stop.synchronize()
+            times[name].append(start.elapsed_time(stop) * 1e-3 / calls)
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    emit(row="k6_box", workload=f"pair-distance variance, {T} frames x {N} atoms, float64, cell side {side:g}",
+         timing=f"device events, {calls} calls per window, median of {windows} windows, forms in turn",
+         open_s=med["open"], box_s=med["box"], box_per_frame_s=med["box_per_frame"],
+         box_over_open=med["box"] / med["open"], box_per_frame_over_open=med["box_per_frame"] / med["open"],
+         windows_s=times)
 
 
 def bench_stream():
