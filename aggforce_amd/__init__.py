@@ -19,6 +19,7 @@ from .qp import (
     stagedjforcegauss_map,
 )
 from .map import LinearMap
+from .pbc import MoleculeTree, make_whole
 
 __version__ = "0.1.0"
 
@@ -33,4 +34,6 @@ __all__ = [
     "stagedjslicegauss_map",
     "stagedjforcegauss_map",
     "LinearMap",
+    "MoleculeTree",
+    "make_whole",
 ]

@@ -1,5 +1,5 @@
-"""Differentiable map application, pair distances and radial basis: thirteen ``torch.autograd.Function``s over the HIP
-kernels.
+"""Differentiable map application, pair distances, radial basis and the unwrap: fourteen ``torch.autograd.Function``s
+over the HIP kernels.
 
 Each Function is one kernel launch; the backward of each calls only these same Functions, so the set is closed under
 differentiation (``gradgradcheck``, force-matching double backward).  Shapes: points (T, N, 3), a 2-D map (n_cg, N),
@@ -54,6 +54,9 @@ Basis(S, D, q)              out[e, col0 + k] = S[e] g_k^(q)(D[e])    (K10a)  dS 
 BasisDot(H, D, q)           out[e] = sum_k H[., k] g_k^(q)(D[e])     (K10b)  dH = Basis(G, D, q),
                             H per element, slotted row or slot table         dD = G * BasisDot(H, D, q + 1)
 ==========================  ===============================================  ==========================================
+
+MakeWhole(X, box, tree) (``pbc.make_whole``): out = X - k L on K11, k the integer image counts along the bond forest.
+The shift is piecewise constant in X, so the backward is the identity (dX = H) and needs no kernel; box is a constant.
 
 A zero distance has weight 0: torch's own first-order value at |0|, and what keeps every higher order finite (the
 diagonal of a self-distance matrix does not depend on X at all).  A first-order backward of a distance (grad mode off)
@@ -466,3 +469,19 @@ class BasisDot(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dD = _as(G * BasisDot.apply(H, D, ctx.q + 1, ctx.spec, ctx.collapse), D.dtype)
         return dH, dD, None, None, None
+
+
+class MakeWhole(torch.autograd.Function):
+    """X (T, N, 3) with the molecules of ``tree`` (a ``pbc.MoleculeTree``, or its ``_kernels.TreeTables``) made whole
+    under ``box`` ((3,) or (T, 3) tensor on X's device, a constant) on K11 (``aggf_make_whole``), in X's dtype.  Every
+    atom moves by a whole number of box lengths, a piecewise constant function of X: the backward is the identity.
+    ``form``: ``_kernels.WHOLE_*`` (tests); ``images``: a (T, N, 3) int32 tensor that receives the image counts."""
+
+    @staticmethod
+    def forward(ctx, X, box, tree, form=K.WHOLE_AUTO, images=None):
+        tab = tree.on(X.device) if hasattr(tree, "on") else tree
+        return K.make_whole(X.contiguous(), _box_kw(box, X.dtype)["box"], tab, images=images, _form=form)
+
+    @staticmethod
+    def backward(ctx, H):
+        return H, None, None, None, None

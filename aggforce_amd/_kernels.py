@@ -1347,6 +1347,67 @@ def pair_min(x: torch.Tensor, c: torch.Tensor, square: bool = False, box: Option
     return out
 
 
+# ------------------------------------------------------------------ K11 whole molecules (aggforce_amd/pbc.py)
+WHOLE_AUTO, WHOLE_LDS, WHOLE_GLOBAL = 0, 1, 2
+_WHOLE_WS_BYTES = 256 << 20  # the global form's count buffers: frames beyond this go in further calls
+
+
+class TreeTables:
+    """A spanning forest on one device (built by ``pbc.MoleculeTree``): ``parent`` (N,) int32, -1 a root, and
+    ``jumps`` (rounds, N) int32, jumps[r][i] the 2^r-th ancestor of i or -1."""
+
+    def __init__(self, parent: torch.Tensor, jumps: torch.Tensor):
+        self.parent, self.jumps = parent, jumps
+        self.n, self.rounds = int(parent.shape[0]), int(jumps.shape[0])
+
+
+def whole_lds_max_sites() -> int:
+    """The largest number of atoms the LDS form of K11 takes (no GPU needed)."""
+    return int(_lib.load().aggf_make_whole_lds_max_sites())
+
+
+def make_whole(x: torch.Tensor, box: torch.Tensor, tree: TreeTables, out: Optional[torch.Tensor] = None,
+               images: Optional[torch.Tensor] = None, _form: int = WHOLE_AUTO) -> torch.Tensor:
+    """(T, N, 3): x with every molecule of ``tree`` made whole under ``box`` ((3,) or (T, 3), x's dtype), K11
+    (aggf_make_whole).  ``out``: where to write (x itself: in place; default a new tensor); ``images``: a (T, N, 3)
+    int32 tensor that receives the image counts.  ``_form`` (tests, benchmarks): WHOLE_LDS or WHOLE_GLOBAL instead of
+    the library's choice."""
+    if x.dim() != 3 or x.shape[2] != 3 or x.dtype not in (torch.float32, torch.float64) or not x.is_contiguous():
+        raise ValueError(f"make_whole: x {tuple(x.shape)} {x.dtype} must be a contiguous (T, N, 3) float32/float64 tensor")
+    stride = _box_arg("make_whole", box, x)
+    T, N = int(x.shape[0]), int(x.shape[1])
+    if N != tree.n or tree.parent.device != x.device:
+        raise ValueError(f"make_whole: a tree over {tree.n} atoms on {tree.parent.device} with x {tuple(x.shape)} on "
+                         f"{x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError("make_whole: out must match x in shape, dtype and device, and be contiguous")
+    if images is not None and (tuple(images.shape) != tuple(x.shape) or images.dtype != torch.int32
+                               or images.device != x.device or not images.is_contiguous()):
+        raise ValueError("make_whole: images must be a contiguous int32 tensor of x's shape on x's device")
+    if _form not in (WHOLE_AUTO, WHOLE_LDS, WHOLE_GLOBAL):
+        raise ValueError(f"make_whole: form {_form}")
+    if T == 0 or N == 0:
+        return out
+    l = lib()
+    code = dtype_code(x.dtype)
+    jumps = tree.jumps if tree.rounds else None
+    in_lds = _form == WHOLE_LDS or (_form == WHOLE_AUTO and N <= whole_lds_max_sites())
+    # frames per call: all of them, or what keeps the global form's counts within _WHOLE_WS_BYTES
+    step = T if in_lds else max(1, min(T, _WHOLE_WS_BYTES // max(1, l.aggf_make_whole_workspace_bytes(1, N, tree.rounds, code))))
+    need = 0 if in_lds else l.aggf_make_whole_workspace_bytes(step, N, tree.rounds, code)
+    ws = workspace(need, x.device, "whole") if need else None
+    with _timed("make_whole"):
+        for t0 in range(0, T, step):
+            n = min(step, T - t0)
+            check(l.aggf_make_whole(ptr(x[t0:]), n, N, code, ptr(tree.parent), ptr(jumps), tree.rounds,
+                                    ptr(box[t0:] if stride else box), stride, ptr(out[t0:]),
+                                    None if images is None else ptr(images[t0:]), ptr(ws), need, _form, stream_ptr()),
+                  "aggf_make_whole")
+    return out
+
+
 # ------------------------------------------------------------------ K10 Gaussian radial basis (aggforce_amd/_autograd.py)
 GB_H_ELEM, GB_H_ROW, GB_H_SLOT = 0, 1, 2
 

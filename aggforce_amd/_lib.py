@@ -84,6 +84,9 @@ PROTOTYPES = {
                                           C.c_int, _vp, _i32, _vp, _vp, C.c_int, _vp]),
     "aggf_pair_min_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
     "aggf_pair_min": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _i32, C.c_int, _vp, _vp, _sz, _vp]),
+    "aggf_make_whole_lds_max_sites": (_i32, []),
+    "aggf_make_whole_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
+    "aggf_make_whole": (C.c_int, [_vp, _i64, _i32, C.c_int, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _sz, C.c_int, _vp]),
     "aggf_gbasis_expand": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _dbl, _dbl, _i32, C.c_int, _vp, _vp]),
     "aggf_gbasis_contract": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _dbl, _dbl, _i32, C.c_int, _vp, _vp]),
     "aggf_gbasis_sum_workspace_bytes": (_sz, [_i64, _i32, _i32]),

@@ -72,6 +72,28 @@ def _checked_box(box, n_steps: int):
     return _as_box(box, int(n_steps))
 
 
+def _whole_coords(coords, box, bonds):
+    """``coords`` with the molecules of ``bonds`` made whole under ``box`` (``pbc.make_whole``, K11), as a GPU tensor.
+    Checked before any device work: ``bonds`` needs ``box`` and ``coords``.  The caller's array is never written: a
+    host array is uploaded and that copy made whole in place, a GPU tensor gets a new one."""
+    from .pbc import as_tree, make_whole
+
+    if box is None:
+        raise ValueError("bonds= makes molecules whole under a periodic box: box= cannot be None.")
+    if coords is None:
+        raise ValueError("bonds= makes the molecules of coords whole: coords cannot be None.")
+    tree = as_tree(bonds, coords.shape[1])
+    box = _checked_box(box, coords.shape[0])
+    if K.is_torch(coords) and coords.is_cuda:
+        dev = K.as_device(coords)
+        own = dev.data_ptr() != coords.data_ptr()  # (a copy as_device had to make: another dtype or layout)
+    else:
+        with K.upload_cache():  # (a cache level of its own: this upload is shared with nobody)
+            dev = K.as_device(coords)
+        own = True
+    return make_whole(dev, box, tree, inplace=own and not dev.requires_grad)
+
+
 def project_forces(
     coords,
     forces,
@@ -79,6 +101,7 @@ def project_forces(
     constrained_inds: Union[Constraints, str, None] = PROJECT_FORCES_CNSTR_AUTO,
     method: Callable[..., TMap] = qp_linear_map,
     box=None,
+    bonds=None,
     **kwargs,
 ) -> Dict[str, Any]:
     """Produce an optimised force map and the mapped trajectory (reference agg.py:49-136).
@@ -94,12 +117,23 @@ def project_forces(
     (n_steps, 3), for coordinates that are wrapped into it.  It is used by the "auto" guess alone, which then
     measures minimum-image distances (``guess_pairwise_constraints(..., box=)``) and so keeps the rigid pairs
     that straddle a face of the cell in some frames; with explicit constraints or None its shape is checked and
-    it is otherwise ignored.  It changes nothing else: mapped coordinates are still ``coord_map`` applied to
-    the coordinates as given -- exact for slice maps, and the caller's business for averaging maps of molecules
-    that the wrap has split (unwrap those first) -- and featurisers (``gb_feat``) still see open distances.
+    it is otherwise ignored.  On its own it changes nothing else: mapped coordinates are still ``coord_map``
+    applied to the coordinates as given -- exact for slice maps, off by a box length for averaging maps of
+    molecules that the wrap has split (pass ``bonds``) -- and featurisers (``gb_feat``) still see open distances.
+
+    ``bonds`` (extra; not forwarded to ``method``; needs ``box`` and ``coords``, ``ValueError`` otherwise, before any
+    device work): the bond graph of the molecules, a ``pbc.MoleculeTree``, a ``jaxutil.PairList`` or a (k, 2)
+    integer array.  The coordinates are then made whole once (``pbc.make_whole``: every atom at the minimum image of
+    its parent in a spanning forest of the bonds, as ``gmx trjconv -pbc whole`` does; the caller's array is not
+    written) and everything downstream sees whole molecules: the guess (which still gets ``box``), ``Trajectory``,
+    ``coord_map`` and the featurisers.  ``gb_feat`` still measures open distances: right for whole molecules
+    smaller than half the cell, still wrong between molecules.  With ``bonds=None`` nothing changes.
 
     Returns a dict with keys mapped_coords, mapped_forces, tmap, residual, constraints.
     """
+    given_coords = coords
+    if bonds is not None:
+        coords = _whole_coords(coords, box, bonds)
     if isinstance(constrained_inds, str) and constrained_inds == PROJECT_FORCES_CNSTR_AUTO:
         if coords is None:
             raise ValueError(
@@ -159,6 +193,8 @@ def project_forces(
             residual = _mean_square(fused_ss, int(np.prod(mapped_forces.shape)), kwargs.get("comm"))
         else:
             residual = force_smoothness(mapped_forces, comm=kwargs.get("comm"))
+    if coords is not given_coords and K.is_torch(mapped_coords):  # (the container of the coordinates as given)
+        mapped_coords = K.like_input(mapped_coords, given_coords)
     return {
         PROJCOORDS_KNAME: mapped_coords,
         PROJFORCES_KNAME: mapped_forces,
@@ -311,6 +347,7 @@ def project_forces_grid_cv(
     method_rng=None,
     cv_noise=None,
     box=None,
+    bonds=None,
     **kwargs,
 ) -> Dict[str, Dict[NamedTuple, T]]:
     """Grid cross-validation over project_forces arguments (reference agg.py:142-235).
@@ -337,8 +374,13 @@ def project_forces_grid_cv(
     subset its box -- a (3,) box as it is, a per-frame box indexed with the training frames -- for the "auto"
     guess.  The one-pass forms take explicit constraints, so the box has no effect on them and does not keep a
     call from them.
+
+    ``bonds`` (extra): as in ``project_forces``; needs ``box`` and ``coords``.  All frames are made whole once, before
+    the folds are taken, and every form -- the loop and the one-pass ones -- works on the whole coordinates.
     """
     n_frames = forces.shape[0]
+    if bonds is not None:
+        coords = _whole_coords(coords, box, bonds)
     if box is not None:
         box = _checked_box(box, n_frames)
     frames = np.arange(n_frames)

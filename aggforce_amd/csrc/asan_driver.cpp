@@ -507,6 +507,49 @@ int main() {
             if (wg <= WS) RUNS(aggf_gbasis_sum(p, p, p, i32, i32, N, T, N, n_slots, nb, 1.3, 1e-3, q, dt, d, ws, wg, nullptr));
             if (w1 <= WS) RUNS(aggf_gbasis_sum(p, nullptr, p, nullptr, nullptr, 0, T, N, 1, nb, 1.3, 1e-3, q, dt, d, ws, w1, nullptr));
           }
+  // K11: the count buffers' size over the grid of shapes (overflowing ones give 0), refusals (NULL box or pointers, bad
+  // stride / dtype / rounds / form, rounds without tables, an N beyond the LDS form, short or misaligned workspaces),
+  // empty shapes, and plausible calls in every dtype / form / stride with the queried workspace, in place and not
+  const int32_t lds_max = aggf_make_whole_lds_max_sites();
+  for (int64_t T : Ts)
+    for (int32_t N : Ns)
+      for (int32_t R : {0, 1, 16}) sink += aggf_make_whole_workspace_bytes(T, N, R, 0) + aggf_make_whole_workspace_bytes(T, N, R, 1);
+  sink += aggf_make_whole_workspace_bytes(INT64_MAX, INT32_MAX, 16, 1) + aggf_make_whole_workspace_bytes(-1, 5, 0, 0) +
+          aggf_make_whole_workspace_bytes(5, 5, -1, 0);
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, nullptr, 0, d, nullptr, ws, WS, 0, nullptr));        // no box
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 1, d, nullptr, ws, WS, 0, nullptr));              // stride
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, -3, d, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, 7, 5, 2, i32, i32, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));              // dtype
+  REFUSED(aggf_make_whole(nullptr, 7, 5, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, 7, 5, 1, nullptr, i32, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 3, nullptr, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, nullptr, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));          // rounds, no tables
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, -1, p, 3, d, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 17, p, 3, d, nullptr, ws, WS, 0, nullptr));             // depth >= 2^16
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, 3, nullptr));              // form
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, -1, nullptr));
+  REFUSED(aggf_make_whole(p, -1, 5, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, 7, -5, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));
+  REFUSED(aggf_make_whole(p, INT64_MAX / 4, 5, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, 0, nullptr));  // T N
+  REFUSED(aggf_make_whole(p, 2, lds_max + 1, 1, i32, i32, 2, p, 3, d, nullptr, ws, WS, 1, nullptr));    // beyond the LDS form
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 3, d, nullptr, ws, 0, 2, nullptr));               // global, no workspace
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 3, d, nullptr, nullptr, WS, 2, nullptr));
+  REFUSED(aggf_make_whole(p, 7, 5, 1, i32, i32, 2, p, 3, d, nullptr, (char*)ws + 2, WS - 2, 2, nullptr));
+  REFUSED(aggf_make_whole(p, 2, lds_max + 1, 0, i32, i32, 2, p, 0, d, nullptr, ws, 64, 0, nullptr));    // auto goes global
+  RUNS(aggf_make_whole(nullptr, 0, 5, 1, nullptr, nullptr, 0, p, 3, nullptr, nullptr, nullptr, 0, 0, nullptr));
+  RUNS(aggf_make_whole(nullptr, 7, 0, 0, nullptr, nullptr, 3, p, 0, nullptr, nullptr, nullptr, 0, 2, nullptr));
+  for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)2000, (int64_t)100000})
+    for (int32_t N : {1, 65, 1366, 4096, lds_max, lds_max + 1, 20000})
+      for (int dt = 0; dt < 2; ++dt)
+        for (int32_t R : {0, 1, 9})
+          for (int32_t bs : {0, 3})
+            for (int form = 0; form < 3; ++form) {
+              if (form == 1 && N > lds_max) continue;
+              const size_t wm = aggf_make_whole_workspace_bytes(T, N, R, dt);
+              if (wm > WS) continue;
+              RUNS(aggf_make_whole(p, T, N, dt, i32, i32, R, p, bs, (char*)p + 8192, i32 + 4096, ws, wm, form, nullptr));
+              RUNS(aggf_make_whole(p, T, N, dt, i32, R ? i32 : nullptr, R, p, bs, p, nullptr, ws, wm, form, nullptr));
+            }
   free(raw);
   printf("%d calls, %d unexpected statuses\n", n_calls, n_bad);
   return n_bad ? 1 : 0;

@@ -595,6 +595,42 @@ int aggf_gbasis_sum(const void* d, const void* s, const void* centers, const int
                     size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K11  Make molecules whole under a periodic box (aggforce_amd.make_whole, project_forces(..., bonds=)):
+ * the unwrap along a bond graph of `gmx trjconv -pbc whole`, for coordinates that are wrapped into an
+ * orthorhombic cell.  X and out: (T, N, 3) in `dtype`; `box` as in the K9c / K9d box forms ((T, 3) with
+ * box_stride 3 or (3,) with box_stride 0, on the device in `dtype`; NULL or another stride: AGGF_ERR_ARG).
+ * The bond graph is a spanning forest: parent[i] in [-1, N) (int32, device), -1 a root; parents may have
+ * larger indices than their children.  Per frame and Cartesian component
+ *     n_i = 0 for a root, else (int) rint((x_i - x_parent(i)) * invL)     invL = 1 / L, `dtype` arithmetic,
+ *     k_i = n_i + the n of every ancestor of i                            nearest even; exact integer sum
+ *     out_i = fma(-(T)k_i, L, x_i)                                        one rounding
+ * The sums along the root paths are formed by pointer jumping: jumps (rounds, N) int32 on the device,
+ * jumps[r][i] = the 2^r-th ancestor of i or -1, rounds the smallest R with 2^R >= the forest's depth (0 for
+ * a forest of roots: jumps may be NULL).  The counts are integers, so they do not depend on schedule or
+ * form.  A root never moves; where every count is 0 (no bonds; a molecule that is whole already and whose
+ * bond components are far below L / 2) out is X bit for bit.  out may be X.  images (nullable): (T, N, 3)
+ * int32, the k_i.
+ *   A box length that is not a positive finite number makes its frame's coordinates NaN and its counts 0; no
+ * other frame is affected.  A non-finite (x_i - x_parent) * invL gives n_i = 0: a non-finite coordinate
+ * passes through to its own output only.  |n_i| is clamped to 2^15 before summing and rounds is at most 16
+ * (a depth of 2^16 or more is refused), so no int32 sum overflows.  THAT IS THE BOUND: a molecule that
+ * extends over more than 32768 cells between two bonded atoms gets a wrong -- defined, finite -- result.
+ * Every index read from parent and jumps is tested against N: an atom with one out of range on its path
+ * gets NaN coordinates (and INT32_MIN image counts) instead of a read outside the arrays.
+ *   form 0: the library's choice; 1: the LDS form, one launch, a workgroup keeps the counts of whole frames
+ * in LDS (at most aggf_make_whole_lds_max_sites() atoms: AGGF_ERR_ARG beyond); 2: the global form, any N, the
+ * counts in ws (one launch for the edge counts, one per round, one for the shift).  ws_bytes >= the query's
+ * value for form 2, and for form 0 beyond the LDS bound (short: AGGF_ERR_WORKSPACE); otherwise ws may be
+ * NULL.  No atomics; nothing reads another workgroup's writes within a launch.  T or N zero returns AGGF_OK
+ * without a launch.
+ * ------------------------------------------------------------------------- */
+int32_t aggf_make_whole_lds_max_sites(void);
+size_t aggf_make_whole_workspace_bytes(int64_t T, int32_t N, int32_t rounds, int dtype);
+int aggf_make_whole(const void* X, int64_t T, int32_t N, int dtype, const int32_t* parent, const int32_t* jumps,
+                    int32_t rounds, const void* box, int32_t box_stride, void* out, int32_t* images, void* ws,
+                    size_t ws_bytes, int form, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K4b/K4c  Dense-featuriser contractions of qp_feat_linear_map (any featuriser that
  * follows the reference's protocol: feats (T, N, n_feat), divs (T, n_feat, 3) per site).
  *
