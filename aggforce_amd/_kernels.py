@@ -763,7 +763,12 @@ def _gb_dtype(Pg, cg, centers) -> int:
     return dtype_code(Pg.dtype)
 
 
-def gb_channels(Pg, cg, site: int, sizes, n_ch: int, centers, width: float, clip: float):
+def gb_channels(Pg, cg, site: int, sizes, n_ch: int, centers, width: float, clip: float,
+                box: Optional[torch.Tensor] = None):
+    """(gauss (T, n_ch, n_basis), grad (T, n_ch, n_basis, 3)) of one cg site; see aggf_gb_channels.  ``box`` ((3,) or
+    (T, 3), the feature dtype; the same for every K4 function that takes one): distances and directions are those of
+    the minimum image under that orthorhombic box (aggf_gb_channels_pbc); a frame whose box is bad is NaN."""
+    stride = None if box is None else _box_arg("gb_channels", box, Pg)
     l = lib()
     T, G, _ = Pg.shape
     nb = centers.numel()
@@ -772,11 +777,18 @@ def gb_channels(Pg, cg, site: int, sizes, n_ch: int, centers, width: float, clip
     grad = torch.empty((T, n_ch, nb, 3), dtype=Pg.dtype, device=Pg.device)
     if T == 0 or n_ch == 0:
         return gauss, grad
-    check(
-        l.aggf_gb_channels(ptr(Pg), ptr(cg), gd, T, G, cg.shape[1], site, ptr(sizes), n_ch, ptr(centers), nb,
-                           float(width), float(clip), ptr(gauss), ptr(grad), stream_ptr()),
-        "aggf_gb_channels",
-    )
+    if box is None:
+        check(
+            l.aggf_gb_channels(ptr(Pg), ptr(cg), gd, T, G, cg.shape[1], site, ptr(sizes), n_ch, ptr(centers), nb,
+                               float(width), float(clip), ptr(gauss), ptr(grad), stream_ptr()),
+            "aggf_gb_channels",
+        )
+    else:
+        check(
+            l.aggf_gb_channels_pbc(ptr(Pg), ptr(cg), gd, T, G, cg.shape[1], site, ptr(sizes), n_ch, ptr(centers), nb,
+                                   float(width), float(clip), ptr(box), stride, ptr(gauss), ptr(grad), stream_ptr()),
+            "aggf_gb_channels_pbc",
+        )
     return gauss, grad
 
 
@@ -796,7 +808,11 @@ def gb_regmat(Fg, Pg, cg, site: int, sizes, n_id: int, n_ch: int, centers, width
     return out
 
 
-def gb_apply(Fg, Pg, cg, sizes, n_id: int, n_ch: int, centers, width: float, clip: float, coef: torch.Tensor):
+def gb_apply(Fg, Pg, cg, sizes, n_id: int, n_ch: int, centers, width: float, clip: float, coef: torch.Tensor,
+             box: Optional[torch.Tensor] = None):
+    """(T, n_cg, 3) float64: the [id | gb] feature-linear map applied; see aggf_gb_apply, and aggf_gb_apply_pbc for
+    ``box`` (as ``gb_channels``)."""
+    stride = None if box is None else _box_arg("gb_apply", box, Pg)
     l = lib()
     T, G, _ = Fg.shape
     n_cg = cg.shape[1]
@@ -804,13 +820,21 @@ def gb_apply(Fg, Pg, cg, sizes, n_id: int, n_ch: int, centers, width: float, cli
     if T == 0:
         return out
     with _timed("gb_apply"):
-        check(
-            l.aggf_gb_apply(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T, G, n_cg,
-                            ptr(sizes), n_id, n_ch,
-                            ptr(centers), centers.numel(), float(width), float(clip), ptr(coef), coef.shape[1],
-                            ptr(out), stream_ptr()),
-            "aggf_gb_apply",
-        )
+        if box is None:
+            check(
+                l.aggf_gb_apply(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T, G, n_cg,
+                                ptr(sizes), n_id, n_ch,
+                                ptr(centers), centers.numel(), float(width), float(clip), ptr(coef), coef.shape[1],
+                                ptr(out), stream_ptr()),
+                "aggf_gb_apply",
+            )
+        else:
+            check(
+                l.aggf_gb_apply_pbc(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T, G,
+                                    n_cg, ptr(sizes), n_id, n_ch, ptr(centers), centers.numel(), float(width),
+                                    float(clip), ptr(coef), coef.shape[1], ptr(box), stride, ptr(out), stream_ptr()),
+                "aggf_gb_apply_pbc",
+            )
     return out
 
 
@@ -826,21 +850,34 @@ def gb_compact_coefficients(coef: np.ndarray, n_id: int, device):
     return (to(coef[:, :n_id]) if n_id else None, to(ptr_h), to(cols.astype(np.int32)), to(gauss[rows, cols]))
 
 
-def gb_apply_cols(Fg, Pg, cg, sizes, n_id: int, centers, width: float, clip: float, compact):
-    """gb_apply from the compact coefficient list of :func:`gb_compact_coefficients`; see aggf_gb_apply_cols."""
+def gb_apply_cols(Fg, Pg, cg, sizes, n_id: int, centers, width: float, clip: float, compact,
+                  box: Optional[torch.Tensor] = None):
+    """gb_apply from the compact coefficient list of :func:`gb_compact_coefficients`; see aggf_gb_apply_cols, and
+    aggf_gb_apply_cols_pbc for ``box`` (as ``gb_channels``)."""
     coef_id, col_ptr, col_idx, col_val = compact
     T, G, _ = Fg.shape
     n_cg = cg.shape[1]
+    stride = None if box is None else _box_arg("gb_apply_cols", box, Pg)
     out = torch.empty((T, n_cg, 3), dtype=torch.float64, device=Fg.device)
     if T == 0:
         return out
     with _timed("gb_apply"):
-        check(
-            lib().aggf_gb_apply_cols(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T, G,
-                                     n_cg, ptr(sizes), n_id, ptr(coef_id), ptr(col_ptr), ptr(col_idx), ptr(col_val),
-                                     ptr(centers), centers.numel(), float(width), float(clip), ptr(out), stream_ptr()),
-            "aggf_gb_apply_cols",
-        )
+        if box is None:
+            check(
+                lib().aggf_gb_apply_cols(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T,
+                                         G, n_cg, ptr(sizes), n_id, ptr(coef_id), ptr(col_ptr), ptr(col_idx),
+                                         ptr(col_val), ptr(centers), centers.numel(), float(width), float(clip),
+                                         ptr(out), stream_ptr()),
+                "aggf_gb_apply_cols",
+            )
+        else:
+            check(
+                lib().aggf_gb_apply_cols_pbc(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers),
+                                             T, G, n_cg, ptr(sizes), n_id, ptr(coef_id), ptr(col_ptr), ptr(col_idx),
+                                             ptr(col_val), ptr(centers), centers.numel(), float(width), float(clip),
+                                             ptr(box), stride, ptr(out), stream_ptr()),
+                "aggf_gb_apply_cols_pbc",
+            )
     return out
 
 
@@ -951,34 +988,54 @@ def gb_constraint_gram(M2: torch.Tensor, gauss: Optional[torch.Tensor], S: int, 
     return out
 
 
-def gb_distance_range(Pg: torch.Tensor, cg: torch.Tensor, n_ch: int):
+def gb_distance_range(Pg: torch.Tensor, cg: torch.Tensor, n_ch: int, box: Optional[torch.Tensor] = None):
     """(rmin, rmax) (n_cg, G) float32: range over frames of every channel's distance to every cg site
-    (evaluated in float32 whatever the feature dtype: the caller applies a safety margin)."""
+    (evaluated in float32 whatever the feature dtype: the caller applies a safety margin).  ``box`` (as
+    ``gb_channels``, in the dtype of ``Pg``): the range of the minimum-image distances (aggf_gb_distance_range_pbc),
+    none of which exceeds half the cell's diagonal."""
+    stride = None if box is None else _box_arg("gb_distance_range", box, Pg)
     if Pg.dtype != torch.float32:
         Pg, cg = Pg.to(torch.float32), cg.to(torch.float32)
+        box = None if box is None else box.to(torch.float32)
     T, G, _ = Pg.shape
     n_cg = cg.shape[1]
     rmin = torch.full((n_cg, G), float("inf"), dtype=torch.float32, device=Pg.device)
     rmax = torch.zeros((n_cg, G), dtype=torch.float32, device=Pg.device)
     if T and n_ch:
-        check(lib().aggf_gb_distance_range(ptr(Pg), ptr(cg), T, G, n_cg, n_ch, ptr(rmin), ptr(rmax), stream_ptr()),
-              "aggf_gb_distance_range")
+        if box is None:
+            check(lib().aggf_gb_distance_range(ptr(Pg), ptr(cg), T, G, n_cg, n_ch, ptr(rmin), ptr(rmax), stream_ptr()),
+                  "aggf_gb_distance_range")
+        else:
+            check(lib().aggf_gb_distance_range_pbc(ptr(Pg), ptr(cg), T, G, n_cg, n_ch, ptr(box), stride, ptr(rmin),
+                                                   ptr(rmax), stream_ptr()), "aggf_gb_distance_range_pbc")
     return rmin, rmax
 
 
 def gb_regmat_cols(Fg, Pg, cg, site: int, sizes, n_id: int, cols: torch.Tensor, centers, width: float, clip: float,
-                   kbt: float, out: torch.Tensor) -> torch.Tensor:
-    """Compact regression matrix of one cg site (listed Gaussian columns only); see aggf_gb_regmat_cols."""
+                   kbt: float, out: torch.Tensor, box: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Compact regression matrix of one cg site (listed Gaussian columns only); see aggf_gb_regmat_cols, and
+    aggf_gb_regmat_cols_pbc for ``box`` (as ``gb_channels``)."""
     T, G, _ = Fg.shape
+    stride = None if box is None else _box_arg("gb_regmat_cols", box, Pg)
     with _timed("gb_regmat"):
-        check(
-            lib().aggf_gb_regmat_cols(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T, G,
-                                      cg.shape[1], site,
-                                      ptr(sizes), n_id, ptr(cols), int(cols.numel()), ptr(centers), centers.numel(),
-                                      float(width), float(clip), float(kbt), out.shape[1], ptr(out),
-                                      dtype_code(out.dtype), stream_ptr()),
-            "aggf_gb_regmat_cols",
-        )
+        if box is None:
+            check(
+                lib().aggf_gb_regmat_cols(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T,
+                                          G, cg.shape[1], site,
+                                          ptr(sizes), n_id, ptr(cols), int(cols.numel()), ptr(centers), centers.numel(),
+                                          float(width), float(clip), float(kbt), out.shape[1], ptr(out),
+                                          dtype_code(out.dtype), stream_ptr()),
+                "aggf_gb_regmat_cols",
+            )
+        else:
+            check(
+                lib().aggf_gb_regmat_cols_pbc(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg),
+                                              _gb_dtype(Pg, cg, centers), T, G, cg.shape[1], site, ptr(sizes), n_id,
+                                              ptr(cols), int(cols.numel()), ptr(centers), centers.numel(), float(width),
+                                              float(clip), float(kbt), out.shape[1], ptr(box), stride, ptr(out),
+                                              dtype_code(out.dtype), stream_ptr()),
+                "aggf_gb_regmat_cols_pbc",
+            )
     return out
 
 

@@ -119,15 +119,25 @@ def project_forces(
     that straddle a face of the cell in some frames; with explicit constraints or None its shape is checked and
     it is otherwise ignored.  On its own it changes nothing else: mapped coordinates are still ``coord_map``
     applied to the coordinates as given -- exact for slice maps, off by a box length for averaging maps of
-    molecules that the wrap has split (pass ``bonds``) -- and featurisers (``gb_feat``) still see open distances.
+    molecules that the wrap has split (pass ``bonds``) -- and a featuriser gets its box through its own binding
+    (``gb_feat(box=)``, below), not from here.
 
     ``bonds`` (extra; not forwarded to ``method``; needs ``box`` and ``coords``, ``ValueError`` otherwise, before any
     device work): the bond graph of the molecules, a ``pbc.MoleculeTree``, a ``jaxutil.PairList`` or a (k, 2)
     integer array.  The coordinates are then made whole once (``pbc.make_whole``: every atom at the minimum image of
     its parent in a spanning forest of the bonds, as ``gmx trjconv -pbc whole`` does; the caller's array is not
     written) and everything downstream sees whole molecules: the guess (which still gets ``box``), ``Trajectory``,
-    ``coord_map`` and the featurisers.  ``gb_feat`` still measures open distances: right for whole molecules
-    smaller than half the cell, still wrong between molecules.  With ``bonds=None`` nothing changes.
+    ``coord_map`` and the featurisers.  With ``bonds=None`` nothing changes.
+
+    The featurised fit of a periodic system binds the box in the featuriser as well, so that ``gb_feat`` measures
+    minimum-image distances from a mapped site to the (whole) constraint groups of every molecule::
+
+        project_forces(coords, forces, cmap, box=B, bonds=bonds, method=qp_feat_linear_map,
+                       featurizer=Multifeaturize([id_feat, Curry(gb_feat, outer=..., box=B)]), ...)
+
+    Without that binding ``gb_feat`` measures open distances: right inside whole molecules smaller than half the
+    cell, wrong between molecules that are closer through a face.  A per-frame ``B`` is for exactly these frames (the
+    fitted map then applies to trajectories of that many frames) and is refused with ``comm=``.
 
     Returns a dict with keys mapped_coords, mapped_forces, tmap, residual, constraints.
     """
@@ -373,12 +383,21 @@ def project_forces_grid_cv(
     ``box`` (extra): as in ``project_forces``, for all ``n_frames`` frames.  The loop hands every training
     subset its box -- a (3,) box as it is, a per-frame box indexed with the training frames -- for the "auto"
     guess.  The one-pass forms take explicit constraints, so the box has no effect on them and does not keep a
-    call from them.
+    call from them.  A featuriser's own box (``Curry(gb_feat, ..., box=)``, see ``project_forces``) must be (3,): a
+    per-frame one is refused here, up front, with a ``ValueError`` -- in the one-pass form and in the loop alike, whose
+    training subsets cannot carry it.
 
     ``bonds`` (extra): as in ``project_forces``; needs ``box`` and ``coords``.  All frames are made whole once, before
     the folds are taken, and every form -- the loop and the one-pass ones -- works on the whole coordinates.
     """
     n_frames = forces.shape[0]
+    from .qp.gbfeat import _per_frame, bound_box
+
+    for featurizer in [kwargs.get("featurizer"), *cv_arg_dict.get("featurizer", [])]:
+        if _per_frame(bound_box(featurizer)):
+            raise ValueError("project_forces_grid_cv: the featuriser binds a per-frame box (gb_feat(box=) of shape "
+                             "(n_frames, 3)), which the training subsets of a cross-validation cannot carry; bind a "
+                             "(3,) box")
     if bonds is not None:
         coords = _whole_coords(coords, box, bonds)
     if box is not None:

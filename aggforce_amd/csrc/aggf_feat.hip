@@ -13,6 +13,13 @@
 //   R3[t,(ch,k),d]    = g_k(r) * Fg[t,ch,d] + kbt * div[t,(ch,k),d],  Fg = group force sums
 // with g_k(r) = max(exp(-((r-c_k)/w)^2), clip) - clip.  The float32 arithmetic of the
 // reference (JAX default) is kept for positions, distances and Gaussians.
+//
+// Box forms (gb_*_pbc_kernel; not in the reference): the displacement p[t,ch] - cg[t,c] is replaced by its minimum image
+// under an orthorhombic box per frame (min_image, aggf_common.h; `box` (T, 3) with bstride 3, or (3,) with bstride 0, in
+// the feature dtype), so r is the minimum-image distance and u its direction.  Group means and mapped sites are taken
+// as given: they need whole groups and whole beads (K11).  A frame whose box is bad has NaN features (its Gaussian
+// columns of the regression matrix, its row of the applied map) and the whole distance range.  Each pair of kernels
+// shares one __device__ body; the open ones keep their names, arguments and bits.  gb_regmat_kernel has no box form.
 #include "aggf_common.h"
 
 namespace aggf {
@@ -62,18 +69,40 @@ struct GbProd { typedef double type; };
 template <>
 struct GbProd<float, float> { typedef float type; };
 
-// distance, unit vector and Gaussian row of channel ch at frame t
+// A body shared by an open and a box kernel takes its grid-stride loop bounds from the kernel: read in the __global__
+// function the launch dimensions compile to what they always did (inside a __device__ body the compiler no longer
+// assumes whole workgroups and adds the partial-workgroup look-up to the open kernels' prologues)
+#define GB_FIRST ((int64_t)blockIdx.x * blockDim.x + threadIdx.x)
+#define GB_STEP ((int64_t)gridDim.x * blockDim.x)
+
+// the box of one frame in a box form: lengths, their inverses (formed once per frame) and whether all three are good
 template <typename TG>
+struct GbCell {
+  TG L[3], iL[3];
+  bool ok;
+};
+template <typename TG>
+__device__ __forceinline__ void gb_cell(const TG* __restrict__ box, int32_t bstride, int64_t t, GbCell<TG>& cell) {
+  cell.ok = box_lengths(box + t * bstride, cell.L, cell.iL);
+}
+
+// distance, unit vector and Gaussian row of channel ch at frame t; PBC: of the minimum image under `cell`
+template <typename TG, bool PBC = false>
 __device__ __forceinline__ void gb_geometry(const TG* __restrict__ Pg, const TG* __restrict__ cg,
                                             int64_t t, int32_t G, int32_t ch, int32_t n_cg, int32_t site,
-                                            TG& r, TG u[3]) {
+                                            TG& r, TG u[3], const GbCell<TG>* cell = nullptr) {
   // no fused multiply-add here: whether dx*dx + dy*dy + dz*dz contracts is otherwise decided per kernel the function is
   // inlined into, and the kernels that evaluate a feature (regression matrix, constraint rows, the two application
   // kernels) must agree on it to the last bit -- as the reference's NumPy/JAX float32 arithmetic does
 #pragma clang fp contract(off)
   const TG* p = Pg + (t * G + ch) * 3;
   const TG* c = cg + (t * n_cg + site) * 3;
-  const TG dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
+  TG dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
+  if (PBC) {
+    dx = min_image(dx, cell->L[0], cell->iL[0]);
+    dy = min_image(dy, cell->L[1], cell->iL[1]);
+    dz = min_image(dz, cell->L[2], cell->iL[2]);
+  }
   r = gb_sqrt(dx * dx + dy * dy + dz * dz);
   u[0] = dx / r;  // NaN at r == 0, like the gradient of jnp.linalg.norm
   u[1] = dy / r;
@@ -88,26 +117,32 @@ __device__ __forceinline__ void gb_gauss(const GbParams<TG>& gp, TG r, int k, TG
   g = gb_max(raw, gp.clip) - gp.clip;
   dg = raw > gp.clip ? (TG)-2 * arg / gp.width * raw : (TG)0;
 }
+// (the clip turns a NaN distance into a zero feature: a frame whose box is bad says so instead)
+template <typename TG>
+__device__ __forceinline__ void gb_bad_cell(const GbCell<TG>& cell, TG& g, TG& dg) {
+  if (!cell.ok) g = dg = (TG)__builtin_nan("");
+}
 
 // compact per-channel features: gauss[t,ch,k], grad[t,ch,k,:] = |ch| g_k'(r) u
-template <typename TG>
-__global__ __launch_bounds__(256) void gb_channels_kernel(const TG* __restrict__ Pg,
-                                                          const TG* __restrict__ cg, int64_t T, int32_t G,
-                                                          int32_t n_cg, int32_t site,
-                                                          const float* __restrict__ sizes, int32_t n_ch,
-                                                          GbParams<TG> gp, TG* __restrict__ gauss,
-                                                          TG* __restrict__ grad) {
+template <typename TG, bool PBC>
+__device__ __forceinline__ void gb_channels_body(const TG* __restrict__ Pg, const TG* __restrict__ cg, int64_t T,
+                                                 int32_t G, int32_t n_cg, int32_t site,
+                                                 const float* __restrict__ sizes, int32_t n_ch, GbParams<TG> gp,
+                                                 const TG* __restrict__ box, int32_t bstride, TG* __restrict__ gauss,
+                                                 TG* __restrict__ grad, int64_t first, int64_t step) {
   const int64_t total = T * n_ch;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = first; i < total; i += step) {
     const int64_t t = i / n_ch;
     const int ch = (int)(i - t * n_ch);
     TG r, u[3];
-    gb_geometry(Pg, cg, t, G, ch, n_cg, site, r, u);
+    GbCell<TG> cell;
+    if (PBC) gb_cell(box, bstride, t, cell);
+    gb_geometry<TG, PBC>(Pg, cg, t, G, ch, n_cg, site, r, u, &cell);
     const TG m = (TG)sizes[ch];
     for (int k = 0; k < gp.n_basis; ++k) {
       TG g, dg;
       gb_gauss(gp, r, k, g, dg);
+      if (PBC) gb_bad_cell(cell, g, dg);
       const int64_t o = i * gp.n_basis + k;
       gauss[o] = g;
       grad[o * 3 + 0] = m * dg * u[0];
@@ -115,6 +150,27 @@ __global__ __launch_bounds__(256) void gb_channels_kernel(const TG* __restrict__
       grad[o * 3 + 2] = m * dg * u[2];
     }
   }
+}
+
+template <typename TG>
+__global__ __launch_bounds__(256) void gb_channels_kernel(const TG* __restrict__ Pg,
+                                                          const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                          int32_t n_cg, int32_t site,
+                                                          const float* __restrict__ sizes, int32_t n_ch,
+                                                          GbParams<TG> gp, TG* __restrict__ gauss,
+                                                          TG* __restrict__ grad) {
+  gb_channels_body<TG, false>(Pg, cg, T, G, n_cg, site, sizes, n_ch, gp, nullptr, 0, gauss, grad, GB_FIRST, GB_STEP);
+}
+
+template <typename TG>
+__global__ __launch_bounds__(256) void gb_channels_pbc_kernel(const TG* __restrict__ Pg,
+                                                              const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                              int32_t n_cg, int32_t site,
+                                                              const float* __restrict__ sizes, int32_t n_ch,
+                                                              GbParams<TG> gp, const TG* __restrict__ box,
+                                                              int32_t bstride, TG* __restrict__ gauss,
+                                                              TG* __restrict__ grad) {
+  gb_channels_body<TG, true>(Pg, cg, T, G, n_cg, site, sizes, n_ch, gp, box, bstride, gauss, grad, GB_FIRST, GB_STEP);
 }
 
 // R3 (T, ld_feat, 3): columns [0, n_id) = group force sums (id_feat block, optional), then
@@ -177,10 +233,12 @@ __device__ __forceinline__ void atomic_max_pos_float(float* addr, float v) {
 }
 
 // rmin/rmax (n_cg, G) must be initialised to +inf / 0.  grid = (channel blocks, sites, frame slices).
-// A NaN distance (non-finite coordinates) marks the channel as spanning everything.
-__global__ __launch_bounds__(256) void gb_range_kernel(const float* __restrict__ Pg, const float* __restrict__ cg,
-                                                       int64_t T, int32_t G, int32_t n_cg, int32_t n_ch,
-                                                       float* __restrict__ rmin, float* __restrict__ rmax) {
+// A NaN distance (non-finite coordinates, under a box a bad length too) marks the channel as spanning everything.
+// PBC: the range of the minimum-image distances, which is what the box forms of the feature kernels evaluate.
+template <bool PBC>
+__device__ __forceinline__ void gb_range_body(const float* __restrict__ Pg, const float* __restrict__ cg, int64_t T,
+                                              int32_t G, int32_t n_cg, int32_t n_ch, const float* __restrict__ box,
+                                              int32_t bstride, float* __restrict__ rmin, float* __restrict__ rmax) {
   const int ch = blockIdx.x * blockDim.x + threadIdx.x;
   const int site = blockIdx.y;
   if (ch >= n_ch) return;
@@ -188,7 +246,12 @@ __global__ __launch_bounds__(256) void gb_range_kernel(const float* __restrict__
   for (int64_t t = blockIdx.z; t < T; t += gridDim.z) {
     const float* p = Pg + (t * G + ch) * 3;
     const float* c = cg + (t * n_cg + site) * 3;
-    const float dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
+    float dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
+    if (PBC) {
+      float L[3], iL[3];
+      box_lengths(box + t * bstride, L, iL);
+      dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+    }
     const float r = sqrtf(dx * dx + dy * dy + dz * dz);
     if (!(r == r)) { lo = 0.0f; hi = INFINITY; }
     lo = fminf(lo, r);
@@ -198,23 +261,35 @@ __global__ __launch_bounds__(256) void gb_range_kernel(const float* __restrict__
   atomic_max_pos_float(rmax + (int64_t)site * G + ch, hi);
 }
 
+__global__ __launch_bounds__(256) void gb_range_kernel(const float* __restrict__ Pg, const float* __restrict__ cg,
+                                                       int64_t T, int32_t G, int32_t n_cg, int32_t n_ch,
+                                                       float* __restrict__ rmin, float* __restrict__ rmax) {
+  gb_range_body<false>(Pg, cg, T, G, n_cg, n_ch, nullptr, 0, rmin, rmax);
+}
+
+__global__ __launch_bounds__(256) void gb_range_pbc_kernel(const float* __restrict__ Pg, const float* __restrict__ cg,
+                                                           int64_t T, int32_t G, int32_t n_cg, int32_t n_ch,
+                                                           const float* __restrict__ box, int32_t bstride,
+                                                           float* __restrict__ rmin, float* __restrict__ rmax) {
+  gb_range_body<true>(Pg, cg, T, G, n_cg, n_ch, box, bstride, rmin, rmax);
+}
+
 // Compact regression matrix: column j < n_id = group force sums; column n_id + j = the Gaussian column
 // cols[j] = ch * n_basis + k (only the listed ones).  One thread per (frame, compact column): consecutive
 // threads write consecutive 3-vectors (coalesced), the distance of a channel is recomputed per listed k.
-template <typename TF, typename TG, typename TO>
-__global__ __launch_bounds__(256) void gb_regmat_cols_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
-                                                             const TG* __restrict__ cg, int64_t T, int32_t G,
-                                                             int32_t n_cg, int32_t site,
-                                                             const float* __restrict__ sizes, int32_t n_id,
-                                                             const int32_t* __restrict__ cols, int32_t n_cols,
-                                                             GbParams<TG> gp, double kbt_d, int32_t ld_feat,
-                                                             TO* __restrict__ R3) {
+template <typename TF, typename TG, typename TO, bool PBC>
+__device__ __forceinline__ void gb_regmat_cols_body(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                    const TG* __restrict__ cg, int64_t T, int32_t G, int32_t n_cg,
+                                                    int32_t site, const float* __restrict__ sizes, int32_t n_id,
+                                                    const int32_t* __restrict__ cols, int32_t n_cols, GbParams<TG> gp,
+                                                    double kbt_d, int32_t ld_feat, const TG* __restrict__ box,
+                                                    int32_t bstride, TO* __restrict__ R3, int64_t first,
+                                                    int64_t step) {
   typedef typename GbProd<TF, TG>::type TP;
   const TP kbt = (TP)kbt_d;
   const int per_frame = n_id + n_cols;
   const int64_t total = T * per_frame;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = first; i < total; i += step) {
     const int64_t t = i / per_frame;
     const int j = (int)(i - t * per_frame);
     TO* o = R3 + (t * (int64_t)ld_feat + j) * 3;
@@ -228,14 +303,44 @@ __global__ __launch_bounds__(256) void gb_regmat_cols_kernel(const TF* __restric
     const int full = cols[j - n_id];
     const int ch = full / gp.n_basis, k = full - ch * gp.n_basis;
     TG r, u[3], g, dg;
-    gb_geometry(Pg, cg, t, G, ch, n_cg, site, r, u);
+    GbCell<TG> cell;
+    if (PBC) gb_cell(box, bstride, t, cell);
+    gb_geometry<TG, PBC>(Pg, cg, t, G, ch, n_cg, site, r, u, &cell);
     gb_gauss(gp, r, k, g, dg);
     const TF* f = Fg + (t * G + ch) * 3;
     const TG s = (TG)sizes[ch] * dg;
     o[0] = (TO)((TP)g * (TP)f[0] + kbt * (TP)(s * u[0]));
     o[1] = (TO)((TP)g * (TP)f[1] + kbt * (TP)(s * u[1]));
     o[2] = (TO)((TP)g * (TP)f[2] + kbt * (TP)(s * u[2]));
+    // (a bad box says so AFTER the products: a select in front of them changes which of the multiply-adds the compiler
+    // fuses, and the box form must round as the open one does)
+    if (PBC && !cell.ok) o[0] = o[1] = o[2] = (TO)__builtin_nan("");
   }
+}
+
+template <typename TF, typename TG, typename TO>
+__global__ __launch_bounds__(256) void gb_regmat_cols_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                             const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                             int32_t n_cg, int32_t site,
+                                                             const float* __restrict__ sizes, int32_t n_id,
+                                                             const int32_t* __restrict__ cols, int32_t n_cols,
+                                                             GbParams<TG> gp, double kbt_d, int32_t ld_feat,
+                                                             TO* __restrict__ R3) {
+  gb_regmat_cols_body<TF, TG, TO, false>(Fg, Pg, cg, T, G, n_cg, site, sizes, n_id, cols, n_cols, gp, kbt_d, ld_feat,
+                                         nullptr, 0, R3, GB_FIRST, GB_STEP);
+}
+
+template <typename TF, typename TG, typename TO>
+__global__ __launch_bounds__(256) void gb_regmat_cols_pbc_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                                 const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                                 int32_t n_cg, int32_t site,
+                                                                 const float* __restrict__ sizes, int32_t n_id,
+                                                                 const int32_t* __restrict__ cols, int32_t n_cols,
+                                                                 GbParams<TG> gp, double kbt_d, int32_t ld_feat,
+                                                                 const TG* __restrict__ box, int32_t bstride,
+                                                                 TO* __restrict__ R3) {
+  gb_regmat_cols_body<TF, TG, TO, true>(Fg, Pg, cg, T, G, n_cg, site, sizes, n_id, cols, n_cols, gp, kbt_d, ld_feat,
+                                        box, bstride, R3, GB_FIRST, GB_STEP);
 }
 
 // CLAMap application of the [id | gb] feature-linear map (featlinearmap.py:512-520,
@@ -248,17 +353,19 @@ __global__ __launch_bounds__(256) void gb_regmat_cols_kernel(const TF* __restric
 constexpr int GB_FR = 4;
 constexpr int GB_CB = 8;  // coefficients of a channel held in registers (basis functions beyond: read in the loop)
 
-template <typename TF, typename TG>
-__global__ __launch_bounds__(256) void gb_apply_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
-                                                       const TG* __restrict__ cg, int64_t T, int32_t G,
-                                                       int32_t n_cg, const float* __restrict__ sizes,
-                                                       int32_t n_id, int32_t n_ch, GbParams<TG> gp,
-                                                       const double* __restrict__ coef, int32_t n_feat,
-                                                       double* __restrict__ out) {
+// PBC: the boxes of the GB_FR frames are read once per (frame block, site), before the channels; a frame whose box is
+// bad gets a NaN row whatever its coefficients.
+template <typename TF, typename TG, bool PBC>
+__device__ __forceinline__ void gb_apply_body(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                              const TG* __restrict__ cg, int64_t T, int32_t G, int32_t n_cg,
+                                              const float* __restrict__ sizes, int32_t n_id, int32_t n_ch,
+                                              GbParams<TG> gp, const double* __restrict__ coef, int32_t n_feat,
+                                              const TG* __restrict__ box, int32_t bstride, double* __restrict__ out,
+                                              int64_t first, int64_t step) {
   typedef typename GbProd<TF, TG>::type TP;
   const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int64_t wid = first >> 6;
+  const int64_t nw = step >> 6;
   const int64_t n_blk = (T + GB_FR - 1) / GB_FR;
   for (int64_t i = wid; i < n_blk * n_cg; i += nw) {
     const int64_t blk = i / n_cg;  // consecutive waves: the same frames, the sites one after the other
@@ -269,6 +376,12 @@ __global__ __launch_bounds__(256) void gb_apply_kernel(const TF* __restrict__ Fg
     double acc[GB_FR][3];
 #pragma unroll
     for (int f = 0; f < GB_FR; ++f) acc[f][0] = acc[f][1] = acc[f][2] = 0.0;
+    GbCell<TG> cell[GB_FR];
+    if (PBC) {
+#pragma unroll
+      for (int f = 0; f < GB_FR; ++f)
+        if (f < nf) gb_cell(box, bstride, t0 + f, cell[f]);
+    }
     for (int g = lane; g < n_id; g += 64) {
       const double c = cf[g];
 #pragma unroll
@@ -296,7 +409,7 @@ __global__ __launch_bounds__(256) void gb_apply_kernel(const TF* __restrict__ Fg
 #pragma unroll
       for (int f = 0; f < GB_FR; ++f) {
         if (f < nf) {
-          gb_geometry(Pg, cg, t0 + f, G, ch, n_cg, site, r[f], u[f]);
+          gb_geometry<TG, PBC>(Pg, cg, t0 + f, G, ch, n_cg, site, r[f], u[f], &cell[f]);
           const TF* fv = Fg + ((t0 + f) * G + ch) * 3;
           fr[f][0] = (TP)fv[0];
           fr[f][1] = (TP)fv[1];
@@ -333,6 +446,7 @@ __global__ __launch_bounds__(256) void gb_apply_kernel(const TF* __restrict__ Fg
         a2 += __shfl_down(a2, off, 64);
       }
       if (lane == 0 && f < nf) {
+        if (PBC && !cell[f].ok) a0 = a1 = a2 = __builtin_nan("");
         double* o = out + ((t0 + f) * n_cg + site) * 3;
         o[0] = a0;
         o[1] = a1;
@@ -342,25 +456,49 @@ __global__ __launch_bounds__(256) void gb_apply_kernel(const TF* __restrict__ Fg
   }
 }
 
+template <typename TF, typename TG>
+__global__ __launch_bounds__(256) void gb_apply_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                       const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                       int32_t n_cg, const float* __restrict__ sizes,
+                                                       int32_t n_id, int32_t n_ch, GbParams<TG> gp,
+                                                       const double* __restrict__ coef, int32_t n_feat,
+                                                       double* __restrict__ out) {
+  gb_apply_body<TF, TG, false>(Fg, Pg, cg, T, G, n_cg, sizes, n_id, n_ch, gp, coef, n_feat, nullptr, 0, out, GB_FIRST,
+                               GB_STEP);
+}
+
+template <typename TF, typename TG>
+__global__ __launch_bounds__(256) void gb_apply_pbc_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                           const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                           int32_t n_cg, const float* __restrict__ sizes,
+                                                           int32_t n_id, int32_t n_ch, GbParams<TG> gp,
+                                                           const double* __restrict__ coef, int32_t n_feat,
+                                                           const TG* __restrict__ box, int32_t bstride,
+                                                           double* __restrict__ out) {
+  gb_apply_body<TF, TG, true>(Fg, Pg, cg, T, G, n_cg, sizes, n_id, n_ch, gp, coef, n_feat, box, bstride, out, GB_FIRST,
+                              GB_STEP);
+}
+
 // The same map from a COMPACT coefficient list: the fit keeps ~a third of the Gaussian columns (2.1 of 8 basis
 // functions per channel at BASELINE config 4) and different ones for every channel, so in gb_apply_kernel -- lane =
 // channel -- nearly every basis function is executed by the wave for the few lanes that need it.  Here lane = one kept
 // column (ch, k) of the site: no idle lanes; the distance of a channel is recomputed for each of its kept columns
 // (cheaper than the expf it replaces).  col_ptr[n_cg + 1] / col_idx (ch * n_basis + k) / col_val: the non-zero
 // Gaussian coefficients per site; coef_id (n_cg, n_id): the id block, dense.
-template <typename TF, typename TG>
-__global__ __launch_bounds__(256) void gb_apply_cols_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
-                                                            const TG* __restrict__ cg, int64_t T, int32_t G,
-                                                            int32_t n_cg, const float* __restrict__ sizes,
-                                                            int32_t n_id, const double* __restrict__ coef_id,
-                                                            const int32_t* __restrict__ col_ptr,
-                                                            const int32_t* __restrict__ col_idx,
-                                                            const double* __restrict__ col_val, GbParams<TG> gp,
-                                                            double* __restrict__ out) {
+template <typename TF, typename TG, bool PBC>
+__device__ __forceinline__ void gb_apply_cols_body(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                   const TG* __restrict__ cg, int64_t T, int32_t G, int32_t n_cg,
+                                                   const float* __restrict__ sizes, int32_t n_id,
+                                                   const double* __restrict__ coef_id,
+                                                   const int32_t* __restrict__ col_ptr,
+                                                   const int32_t* __restrict__ col_idx,
+                                                   const double* __restrict__ col_val, GbParams<TG> gp,
+                                                   const TG* __restrict__ box, int32_t bstride,
+                                                   double* __restrict__ out, int64_t first, int64_t step) {
   typedef typename GbProd<TF, TG>::type TP;
   const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int64_t wid = first >> 6;
+  const int64_t nw = step >> 6;
   const int64_t n_blk = (T + GB_FR - 1) / GB_FR;
   for (int64_t i = wid; i < n_blk * n_cg; i += nw) {
     const int64_t blk = i / n_cg;
@@ -370,6 +508,12 @@ __global__ __launch_bounds__(256) void gb_apply_cols_kernel(const TF* __restrict
     double acc[GB_FR][3];
 #pragma unroll
     for (int f = 0; f < GB_FR; ++f) acc[f][0] = acc[f][1] = acc[f][2] = 0.0;
+    GbCell<TG> cell[GB_FR];
+    if (PBC) {
+#pragma unroll
+      for (int f = 0; f < GB_FR; ++f)
+        if (f < nf) gb_cell(box, bstride, t0 + f, cell[f]);
+    }
     for (int g = lane; g < n_id; g += 64) {
       const double c = coef_id[(int64_t)site * n_id + g];
 #pragma unroll
@@ -391,7 +535,7 @@ __global__ __launch_bounds__(256) void gb_apply_cols_kernel(const TF* __restrict
       for (int f = 0; f < GB_FR; ++f) {
         if (f < nf) {
           TG r, u[3], g, dg;
-          gb_geometry(Pg, cg, t0 + f, G, ch, n_cg, site, r, u);
+          gb_geometry<TG, PBC>(Pg, cg, t0 + f, G, ch, n_cg, site, r, u, &cell[f]);
           gb_gauss(gp, r, k, g, dg);
           const TF* fv = Fg + ((t0 + f) * G + ch) * 3;
           const TG sd = m * dg;
@@ -411,6 +555,7 @@ __global__ __launch_bounds__(256) void gb_apply_cols_kernel(const TF* __restrict
         a2 += __shfl_down(a2, off, 64);
       }
       if (lane == 0 && f < nf) {
+        if (PBC && !cell[f].ok) a0 = a1 = a2 = __builtin_nan("");
         double* o = out + ((t0 + f) * n_cg + site) * 3;
         o[0] = a0;
         o[1] = a1;
@@ -418,6 +563,33 @@ __global__ __launch_bounds__(256) void gb_apply_cols_kernel(const TF* __restrict
       }
     }
   }
+}
+
+template <typename TF, typename TG>
+__global__ __launch_bounds__(256) void gb_apply_cols_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                            const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                            int32_t n_cg, const float* __restrict__ sizes,
+                                                            int32_t n_id, const double* __restrict__ coef_id,
+                                                            const int32_t* __restrict__ col_ptr,
+                                                            const int32_t* __restrict__ col_idx,
+                                                            const double* __restrict__ col_val, GbParams<TG> gp,
+                                                            double* __restrict__ out) {
+  gb_apply_cols_body<TF, TG, false>(Fg, Pg, cg, T, G, n_cg, sizes, n_id, coef_id, col_ptr, col_idx, col_val, gp, nullptr,
+                                    0, out, GB_FIRST, GB_STEP);
+}
+
+template <typename TF, typename TG>
+__global__ __launch_bounds__(256) void gb_apply_cols_pbc_kernel(const TF* __restrict__ Fg, const TG* __restrict__ Pg,
+                                                                const TG* __restrict__ cg, int64_t T, int32_t G,
+                                                                int32_t n_cg, const float* __restrict__ sizes,
+                                                                int32_t n_id, const double* __restrict__ coef_id,
+                                                                const int32_t* __restrict__ col_ptr,
+                                                                const int32_t* __restrict__ col_idx,
+                                                                const double* __restrict__ col_val, GbParams<TG> gp,
+                                                                const TG* __restrict__ box, int32_t bstride,
+                                                                double* __restrict__ out) {
+  gb_apply_cols_body<TF, TG, true>(Fg, Pg, cg, T, G, n_cg, sizes, n_id, coef_id, col_ptr, col_idx, col_val, gp, box,
+                                   bstride, out, GB_FIRST, GB_STEP);
 }
 
 static inline dim3 feat_grid(int64_t n) {
@@ -430,6 +602,13 @@ static inline dim3 feat_grid(int64_t n) {
 static int check_gb(const void* centers, int32_t n_basis, double width) {
   if (!centers || n_basis <= 0 || n_basis > 64) return fail(AGGF_ERR_ARG, "gb_feat: bad n_basis / centres");
   if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "gb_feat: width must be positive");
+  return AGGF_OK;
+}
+
+// the box of a box form: (T, 3) or (3,) in the feature dtype
+static int check_gb_box(const char* who, const void* box, int32_t box_stride) {
+  if (!box) return fail(AGGF_ERR_ARG, "%s: NULL box", who);
+  if (box_stride != 0 && box_stride != 3) return fail(AGGF_ERR_ARG, "%s: box_stride %d is neither 0 nor 3", who, box_stride);
   return AGGF_OK;
 }
 
@@ -458,24 +637,30 @@ extern "C" int aggf_group_reduce(const void* X, int64_t T, int32_t N, int in_dty
   return AGGF_OK;
 }
 
-extern "C" int aggf_gb_channels(const void* Pg, const void* cg, int g_dtype, int64_t T, int32_t G, int32_t n_cg,
-                                int32_t site, const float* sizes, int32_t n_ch, const void* centers,
-                                int32_t n_basis, double width, double clip, void* gauss, void* grad,
-                                void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (!Pg || !cg || !sizes || !gauss || !grad) return fail(AGGF_ERR_ARG, "aggf_gb_channels: NULL pointer");
+// every K4 entry point below, open (box NULL) or under a box: one validation and one launch plan for both
+static int gb_channels(const char* who, const void* Pg, const void* cg, int g_dtype, int64_t T, int32_t G, int32_t n_cg,
+                       int32_t site, const float* sizes, int32_t n_ch, const void* centers, int32_t n_basis,
+                       double width, double clip, const void* box, int32_t bstride, void* gauss, void* grad,
+                       hipStream_t stream) {
+  if (!Pg || !cg || !sizes || !gauss || !grad) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
   if (T <= 0 || G <= 0 || n_ch <= 0 || n_ch > G || site < 0 || site >= n_cg)
-    return fail(AGGF_ERR_ARG, "aggf_gb_channels: bad shape");
+    return fail(AGGF_ERR_ARG, "%s: bad shape", who);
   int rc = check_gb(centers, n_basis, width);
   if (rc) return rc;
   if (g_dtype == AGGF_F32) {
     GbParams<float> gp{(const float*)centers, n_basis, (float)width, (float)clip};
-    AGGF_LAUNCH(gb_channels_kernel<float>, feat_grid(T * n_ch), dim3(256), 0, stream, (const float*)Pg, (const float*)cg, T, G, n_cg, site, sizes, n_ch, gp, (float*)gauss, (float*)grad);
+    if (box)
+      AGGF_LAUNCH(gb_channels_pbc_kernel<float>, feat_grid(T * n_ch), dim3(256), 0, stream, (const float*)Pg, (const float*)cg, T, G, n_cg, site, sizes, n_ch, gp, (const float*)box, bstride, (float*)gauss, (float*)grad);
+    else
+      AGGF_LAUNCH(gb_channels_kernel<float>, feat_grid(T * n_ch), dim3(256), 0, stream, (const float*)Pg, (const float*)cg, T, G, n_cg, site, sizes, n_ch, gp, (float*)gauss, (float*)grad);
   } else if (g_dtype == AGGF_F64) {
     GbParams<double> gp{(const double*)centers, n_basis, width, clip};
-    AGGF_LAUNCH(gb_channels_kernel<double>, feat_grid(T * n_ch), dim3(256), 0, stream, (const double*)Pg, (const double*)cg, T, G, n_cg, site, sizes, n_ch, gp, (double*)gauss, (double*)grad);
+    if (box)
+      AGGF_LAUNCH(gb_channels_pbc_kernel<double>, feat_grid(T * n_ch), dim3(256), 0, stream, (const double*)Pg, (const double*)cg, T, G, n_cg, site, sizes, n_ch, gp, (const double*)box, bstride, (double*)gauss, (double*)grad);
+    else
+      AGGF_LAUNCH(gb_channels_kernel<double>, feat_grid(T * n_ch), dim3(256), 0, stream, (const double*)Pg, (const double*)cg, T, G, n_cg, site, sizes, n_ch, gp, (double*)gauss, (double*)grad);
   } else {
-    return fail(AGGF_ERR_ARG, "aggf_gb_channels: bad feature dtype");
+    return fail(AGGF_ERR_ARG, "%s: bad feature dtype", who);
   }
   AGGF_LAUNCH_OK();
   return AGGF_OK;
@@ -490,15 +675,15 @@ extern "C" int aggf_gb_channels(const void* Pg, const void* cg, int g_dtype, int
       if (f_dtype == AGGF_F32 && out_dtype == AGGF_F32) { typedef float TF; typedef float TO __attribute__((unused)); LAUNCH; }        \
       else if (f_dtype == AGGF_F32 && out_dtype == AGGF_F64) { typedef float TF; typedef double TO __attribute__((unused)); LAUNCH; }  \
       else if (f_dtype == AGGF_F64 && out_dtype == AGGF_F64) { typedef double TF; typedef double TO __attribute__((unused)); LAUNCH; } \
-      else return fail(AGGF_ERR_ARG, WHO ": bad dtype (out must be the product dtype or float64)");            \
+      else return fail(AGGF_ERR_ARG, "%s: bad dtype (out must be the product dtype or float64)", WHO);         \
     } else if (g_dtype == AGGF_F64) {                                                                          \
       GbParams<double> gp{(const double*)centers, n_basis, width, clip};                                       \
       typedef double TG;                                                                                       \
       if (f_dtype == AGGF_F32 && out_dtype == AGGF_F64) { typedef float TF; typedef double TO __attribute__((unused)); LAUNCH; }       \
       else if (f_dtype == AGGF_F64 && out_dtype == AGGF_F64) { typedef double TF; typedef double TO __attribute__((unused)); LAUNCH; } \
-      else return fail(AGGF_ERR_ARG, WHO ": bad dtype (float64 features give float64 products)");              \
+      else return fail(AGGF_ERR_ARG, "%s: bad dtype (float64 features give float64 products)", WHO);           \
     } else {                                                                                                   \
-      return fail(AGGF_ERR_ARG, WHO ": bad feature dtype");                                                    \
+      return fail(AGGF_ERR_ARG, "%s: bad feature dtype", WHO);                                                 \
     }                                                                                                          \
   } while (0)
 
@@ -514,7 +699,8 @@ extern "C" int aggf_gb_regmat(const void* Fg, int f_dtype, const void* Pg, const
   int rc = check_gb(centers, n_basis, width);
   if (rc) return rc;
   const dim3 grid = feat_grid(T * (n_id + n_ch));
-  AGGF_GB_DISPATCH("aggf_gb_regmat",
+  const char* who = "aggf_gb_regmat";
+  AGGF_GB_DISPATCH(who,
                    AGGF_LAUNCH((gb_regmat_kernel<TF, TG, TO>), grid, dim3(256), 0, stream, (const TF*)Fg,
                                       (const TG*)Pg, (const TG*)cg, T, G, n_cg, site, sizes, n_id, n_ch, gp, kbt,
                                       ld_feat, (TO*)R3));
@@ -522,25 +708,130 @@ extern "C" int aggf_gb_regmat(const void* Fg, int f_dtype, const void* Pg, const
   return AGGF_OK;
 }
 
-extern "C" int aggf_gb_apply(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
-                             int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, int32_t n_ch,
-                             const void* centers, int32_t n_basis, double width, double clip,
-                             const double* coef, int32_t n_feat, double* out, void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (!Fg || !Pg || !cg || !sizes || !coef || !out) return fail(AGGF_ERR_ARG, "aggf_gb_apply: NULL pointer");
+static int gb_apply(const char* who, const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                    int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, int32_t n_ch, const void* centers,
+                    int32_t n_basis, double width, double clip, const double* coef, int32_t n_feat, const void* box,
+                    int32_t bstride, double* out, hipStream_t stream) {
+  if (!Fg || !Pg || !cg || !sizes || !coef || !out) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
   if (T <= 0 || G <= 0 || n_cg <= 0 || n_ch < 0 || n_ch > G || n_id < 0 || n_id > G ||
       n_feat != n_id + n_ch * n_basis)
-    return fail(AGGF_ERR_ARG, "aggf_gb_apply: bad shape");
+    return fail(AGGF_ERR_ARG, "%s: bad shape", who);
   int rc = check_gb(centers, n_basis, width);
   if (rc) return rc;
   const dim3 grid = feat_grid(((T + GB_FR - 1) / GB_FR) * n_cg * 64);
   const int out_dtype = AGGF_F64;
-  AGGF_GB_DISPATCH("aggf_gb_apply",
-                   AGGF_LAUNCH((gb_apply_kernel<TF, TG>), grid, dim3(256), 0, stream, (const TF*)Fg,
+  if (box)
+    AGGF_GB_DISPATCH(who, AGGF_LAUNCH((gb_apply_pbc_kernel<TF, TG>), grid, dim3(256), 0, stream, (const TF*)Fg,
+                                      (const TG*)Pg, (const TG*)cg, T, G, n_cg, sizes, n_id, n_ch, gp, coef, n_feat,
+                                      (const TG*)box, bstride, out));
+  else
+    AGGF_GB_DISPATCH(who, AGGF_LAUNCH((gb_apply_kernel<TF, TG>), grid, dim3(256), 0, stream, (const TF*)Fg,
                                       (const TG*)Pg, (const TG*)cg, T, G, n_cg, sizes, n_id, n_ch, gp, coef, n_feat,
                                       out));
   AGGF_LAUNCH_OK();
   return AGGF_OK;
+}
+
+static int gb_apply_cols(const char* who, const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype,
+                         int64_t T, int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, const double* coef_id,
+                         const int32_t* col_ptr, const int32_t* col_idx, const double* col_val, const void* centers,
+                         int32_t n_basis, double width, double clip, const void* box, int32_t bstride, double* out,
+                         hipStream_t stream) {
+  if (!Fg || !Pg || !cg || !sizes || !col_ptr || !out || (n_id > 0 && !coef_id))
+    return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if (T <= 0 || G <= 0 || n_cg <= 0 || n_id < 0 || n_id > G) return fail(AGGF_ERR_ARG, "%s: bad shape", who);
+  int rc = check_gb(centers, n_basis, width);
+  if (rc) return rc;
+  const dim3 grid = feat_grid(((T + GB_FR - 1) / GB_FR) * n_cg * 64);
+  const int out_dtype = AGGF_F64;
+  if (box)
+    AGGF_GB_DISPATCH(who, AGGF_LAUNCH((gb_apply_cols_pbc_kernel<TF, TG>), grid, dim3(256), 0, stream, (const TF*)Fg,
+                                      (const TG*)Pg, (const TG*)cg, T, G, n_cg, sizes, n_id, coef_id, col_ptr, col_idx,
+                                      col_val, gp, (const TG*)box, bstride, out));
+  else
+    AGGF_GB_DISPATCH(who, AGGF_LAUNCH((gb_apply_cols_kernel<TF, TG>), grid, dim3(256), 0, stream, (const TF*)Fg,
+                                      (const TG*)Pg, (const TG*)cg, T, G, n_cg, sizes, n_id, coef_id, col_ptr, col_idx,
+                                      col_val, gp, out));
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+static int gb_distance_range(const char* who, const float* Pg, const float* cg, int64_t T, int32_t G, int32_t n_cg,
+                             int32_t n_ch, const float* box, int32_t bstride, float* rmin, float* rmax,
+                             hipStream_t stream) {
+  if (!Pg || !cg || !rmin || !rmax) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if (T <= 0 || G <= 0 || n_cg <= 0 || n_cg > 65535 || n_ch <= 0 || n_ch > G)
+    return fail(AGGF_ERR_ARG, "%s: bad shape", who);
+  int64_t slices = ceil_div(T, 256);
+  if (slices > 256) slices = 256;
+  const dim3 grid((unsigned)ceil_div(n_ch, 256), (unsigned)n_cg, (unsigned)slices);
+  if (box)
+    AGGF_LAUNCH(gb_range_pbc_kernel, grid, dim3(256), 0, stream, Pg, cg, T, G, n_cg, n_ch, box, bstride, rmin, rmax);
+  else
+    AGGF_LAUNCH(gb_range_kernel, grid, dim3(256), 0, stream, Pg, cg, T, G, n_cg, n_ch, rmin, rmax);
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+static int gb_regmat_cols(const char* who, const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype,
+                          int64_t T, int32_t G, int32_t n_cg, int32_t site, const float* sizes, int32_t n_id,
+                          const int32_t* cols, int32_t n_cols, const void* centers, int32_t n_basis, double width,
+                          double clip, double kbt, int32_t ld_feat, const void* box, int32_t bstride, void* R3,
+                          int out_dtype, hipStream_t stream) {
+  if (!Fg || !Pg || !cg || !sizes || !R3 || (n_cols > 0 && !cols)) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if (T <= 0 || G <= 0 || n_cols < 0 || n_id < 0 || n_id > G || n_id + n_cols <= 0 || site < 0 || site >= n_cg ||
+      ld_feat < n_id + n_cols)
+    return fail(AGGF_ERR_ARG, "%s: bad shape", who);
+  int rc = check_gb(centers, n_basis, width);
+  if (rc) return rc;
+  const dim3 grid = feat_grid(T * (n_id + n_cols));
+  if (box)
+    AGGF_GB_DISPATCH(who, AGGF_LAUNCH((gb_regmat_cols_pbc_kernel<TF, TG, TO>), grid, dim3(256), 0, stream,
+                                      (const TF*)Fg, (const TG*)Pg, (const TG*)cg, T, G, n_cg, site, sizes, n_id, cols,
+                                      n_cols, gp, kbt, ld_feat, (const TG*)box, bstride, (TO*)R3));
+  else
+    AGGF_GB_DISPATCH(who, AGGF_LAUNCH((gb_regmat_cols_kernel<TF, TG, TO>), grid, dim3(256), 0, stream, (const TF*)Fg,
+                                      (const TG*)Pg, (const TG*)cg, T, G, n_cg, site, sizes, n_id, cols, n_cols, gp, kbt,
+                                      ld_feat, (TO*)R3));
+  AGGF_LAUNCH_OK();
+  return AGGF_OK;
+}
+
+extern "C" int aggf_gb_channels(const void* Pg, const void* cg, int g_dtype, int64_t T, int32_t G, int32_t n_cg,
+                                int32_t site, const float* sizes, int32_t n_ch, const void* centers,
+                                int32_t n_basis, double width, double clip, void* gauss, void* grad,
+                                void* stream_v) {
+  return gb_channels("aggf_gb_channels", Pg, cg, g_dtype, T, G, n_cg, site, sizes, n_ch, centers, n_basis, width, clip,
+                     nullptr, 0, gauss, grad, (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_gb_channels_pbc(const void* Pg, const void* cg, int g_dtype, int64_t T, int32_t G, int32_t n_cg,
+                                    int32_t site, const float* sizes, int32_t n_ch, const void* centers,
+                                    int32_t n_basis, double width, double clip, const void* box, int32_t box_stride,
+                                    void* gauss, void* grad, void* stream_v) {
+  const int rc = check_gb_box("aggf_gb_channels_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return gb_channels("aggf_gb_channels_pbc", Pg, cg, g_dtype, T, G, n_cg, site, sizes, n_ch, centers, n_basis, width,
+                     clip, box, box_stride, gauss, grad, (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_gb_apply(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                             int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, int32_t n_ch,
+                             const void* centers, int32_t n_basis, double width, double clip,
+                             const double* coef, int32_t n_feat, double* out, void* stream_v) {
+  return gb_apply("aggf_gb_apply", Fg, f_dtype, Pg, cg, g_dtype, T, G, n_cg, sizes, n_id, n_ch, centers, n_basis, width,
+                  clip, coef, n_feat, nullptr, 0, out, (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_gb_apply_pbc(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                                 int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, int32_t n_ch,
+                                 const void* centers, int32_t n_basis, double width, double clip,
+                                 const double* coef, int32_t n_feat, const void* box, int32_t box_stride, double* out,
+                                 void* stream_v) {
+  const int rc = check_gb_box("aggf_gb_apply_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return gb_apply("aggf_gb_apply_pbc", Fg, f_dtype, Pg, cg, g_dtype, T, G, n_cg, sizes, n_id, n_ch, centers, n_basis,
+                  width, clip, coef, n_feat, box, box_stride, out, (hipStream_t)stream_v);
 }
 
 extern "C" int aggf_gb_apply_cols(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
@@ -548,34 +839,34 @@ extern "C" int aggf_gb_apply_cols(const void* Fg, int f_dtype, const void* Pg, c
                                   const int32_t* col_ptr, const int32_t* col_idx, const double* col_val,
                                   const void* centers, int32_t n_basis, double width, double clip, double* out,
                                   void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (!Fg || !Pg || !cg || !sizes || !col_ptr || !out || (n_id > 0 && !coef_id))
-    return fail(AGGF_ERR_ARG, "aggf_gb_apply_cols: NULL pointer");
-  if (T <= 0 || G <= 0 || n_cg <= 0 || n_id < 0 || n_id > G) return fail(AGGF_ERR_ARG, "aggf_gb_apply_cols: bad shape");
-  int rc = check_gb(centers, n_basis, width);
-  if (rc) return rc;
-  const dim3 grid = feat_grid(((T + GB_FR - 1) / GB_FR) * n_cg * 64);
-  const int out_dtype = AGGF_F64;
-  AGGF_GB_DISPATCH("aggf_gb_apply_cols",
-                   AGGF_LAUNCH((gb_apply_cols_kernel<TF, TG>), grid, dim3(256), 0, stream, (const TF*)Fg,
-                                      (const TG*)Pg, (const TG*)cg, T, G, n_cg, sizes, n_id, coef_id, col_ptr, col_idx,
-                                      col_val, gp, out));
-  AGGF_LAUNCH_OK();
-  return AGGF_OK;
+  return gb_apply_cols("aggf_gb_apply_cols", Fg, f_dtype, Pg, cg, g_dtype, T, G, n_cg, sizes, n_id, coef_id, col_ptr,
+                       col_idx, col_val, centers, n_basis, width, clip, nullptr, 0, out, (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_gb_apply_cols_pbc(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype,
+                                      int64_t T, int32_t G, int32_t n_cg, const float* sizes, int32_t n_id,
+                                      const double* coef_id, const int32_t* col_ptr, const int32_t* col_idx,
+                                      const double* col_val, const void* centers, int32_t n_basis, double width,
+                                      double clip, const void* box, int32_t box_stride, double* out, void* stream_v) {
+  const int rc = check_gb_box("aggf_gb_apply_cols_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return gb_apply_cols("aggf_gb_apply_cols_pbc", Fg, f_dtype, Pg, cg, g_dtype, T, G, n_cg, sizes, n_id, coef_id, col_ptr,
+                       col_idx, col_val, centers, n_basis, width, clip, box, box_stride, out, (hipStream_t)stream_v);
 }
 
 extern "C" int aggf_gb_distance_range(const float* Pg, const float* cg, int64_t T, int32_t G, int32_t n_cg,
                                       int32_t n_ch, float* rmin, float* rmax, void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (!Pg || !cg || !rmin || !rmax) return fail(AGGF_ERR_ARG, "aggf_gb_distance_range: NULL pointer");
-  if (T <= 0 || G <= 0 || n_cg <= 0 || n_cg > 65535 || n_ch <= 0 || n_ch > G)
-    return fail(AGGF_ERR_ARG, "aggf_gb_distance_range: bad shape");
-  int64_t slices = ceil_div(T, 256);
-  if (slices > 256) slices = 256;
-  const dim3 grid((unsigned)ceil_div(n_ch, 256), (unsigned)n_cg, (unsigned)slices);
-  AGGF_LAUNCH(gb_range_kernel, grid, dim3(256), 0, stream, Pg, cg, T, G, n_cg, n_ch, rmin, rmax);
-  AGGF_LAUNCH_OK();
-  return AGGF_OK;
+  return gb_distance_range("aggf_gb_distance_range", Pg, cg, T, G, n_cg, n_ch, nullptr, 0, rmin, rmax,
+                           (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_gb_distance_range_pbc(const float* Pg, const float* cg, int64_t T, int32_t G, int32_t n_cg,
+                                          int32_t n_ch, const float* box, int32_t box_stride, float* rmin, float* rmax,
+                                          void* stream_v) {
+  const int rc = check_gb_box("aggf_gb_distance_range_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return gb_distance_range("aggf_gb_distance_range_pbc", Pg, cg, T, G, n_cg, n_ch, box, box_stride, rmin, rmax,
+                           (hipStream_t)stream_v);
 }
 
 extern "C" int aggf_gb_regmat_cols(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
@@ -583,19 +874,18 @@ extern "C" int aggf_gb_regmat_cols(const void* Fg, int f_dtype, const void* Pg, 
                                    const int32_t* cols, int32_t n_cols, const void* centers, int32_t n_basis,
                                    double width, double clip, double kbt, int32_t ld_feat, void* R3,
                                    int out_dtype, void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (!Fg || !Pg || !cg || !sizes || !R3 || (n_cols > 0 && !cols))
-    return fail(AGGF_ERR_ARG, "aggf_gb_regmat_cols: NULL pointer");
-  if (T <= 0 || G <= 0 || n_cols < 0 || n_id < 0 || n_id > G || n_id + n_cols <= 0 || site < 0 || site >= n_cg ||
-      ld_feat < n_id + n_cols)
-    return fail(AGGF_ERR_ARG, "aggf_gb_regmat_cols: bad shape");
-  int rc = check_gb(centers, n_basis, width);
-  if (rc) return rc;
-  const dim3 grid = feat_grid(T * (n_id + n_cols));
-  AGGF_GB_DISPATCH("aggf_gb_regmat_cols",
-                   AGGF_LAUNCH((gb_regmat_cols_kernel<TF, TG, TO>), grid, dim3(256), 0, stream, (const TF*)Fg,
-                                      (const TG*)Pg, (const TG*)cg, T, G, n_cg, site, sizes, n_id, cols, n_cols, gp, kbt,
-                                      ld_feat, (TO*)R3));
-  AGGF_LAUNCH_OK();
-  return AGGF_OK;
+  return gb_regmat_cols("aggf_gb_regmat_cols", Fg, f_dtype, Pg, cg, g_dtype, T, G, n_cg, site, sizes, n_id, cols, n_cols,
+                        centers, n_basis, width, clip, kbt, ld_feat, nullptr, 0, R3, out_dtype, (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_gb_regmat_cols_pbc(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype,
+                                       int64_t T, int32_t G, int32_t n_cg, int32_t site, const float* sizes,
+                                       int32_t n_id, const int32_t* cols, int32_t n_cols, const void* centers,
+                                       int32_t n_basis, double width, double clip, double kbt, int32_t ld_feat,
+                                       const void* box, int32_t box_stride, void* R3, int out_dtype, void* stream_v) {
+  const int rc = check_gb_box("aggf_gb_regmat_cols_pbc", box, box_stride);
+  if (rc != AGGF_OK) return rc;
+  return gb_regmat_cols("aggf_gb_regmat_cols_pbc", Fg, f_dtype, Pg, cg, g_dtype, T, G, n_cg, site, sizes, n_id, cols,
+                        n_cols, centers, n_basis, width, clip, kbt, ld_feat, box, box_stride, R3, out_dtype,
+                        (hipStream_t)stream_v);
 }

@@ -131,6 +131,46 @@ int main() {
   REFUSED(aggf_gb_regmat_cols(nullptr, 0, p, p, 0, 10, 5, 2, 0, (float*)p, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, p, 1, nullptr));
   REFUSED(aggf_gb_apply(nullptr, 0, p, p, 0, 10, 5, 2, (float*)p, 5, 4, p, 8, 1.0, 1e-5, d, 37, d, nullptr));
   REFUSED(aggf_gb_apply_cols(nullptr, 0, p, p, 0, 10, 5, 2, (float*)p, 5, d, i32, i32, d, p, 8, 1.0, 1e-5, d, nullptr));
+  // K4 box forms: the box's own refusals (NULL, a stride other than 0 or 3), a bad dtype, a refusal of the open twin;
+  // then with plausible arguments, (3,) and (T, 3), every dtype combination of the dispatch
+  {
+    float* fp = (float*)p;
+    REFUSED(aggf_gb_channels_pbc(p, p, 0, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, nullptr, 3, p, p, nullptr));  // no box
+    REFUSED(aggf_gb_channels_pbc(p, p, 0, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, p, 1, p, p, nullptr));        // stride
+    REFUSED(aggf_gb_channels_pbc(p, p, 0, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, p, -3, p, p, nullptr));
+    REFUSED(aggf_gb_channels_pbc(p, p, 7, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, p, 3, p, p, nullptr));        // dtype
+    REFUSED(aggf_gb_channels_pbc(nullptr, p, 0, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, p, 3, p, p, nullptr));
+    REFUSED(aggf_gb_channels_pbc(p, p, 0, 10, 5, 2, 2, fp, 4, p, 8, 1.0, 1e-5, p, 0, p, p, nullptr));        // site
+    REFUSED(aggf_gb_distance_range_pbc(fp, fp, 10, 5, 2, 4, nullptr, 3, fp, fp, nullptr));
+    REFUSED(aggf_gb_distance_range_pbc(fp, fp, 10, 5, 2, 4, fp, 6, fp, fp, nullptr));
+    REFUSED(aggf_gb_distance_range_pbc(nullptr, fp, 10, 5, 2, 4, fp, 3, fp, fp, nullptr));
+    REFUSED(aggf_gb_distance_range_pbc(fp, fp, 10, 5, 2, 6, fp, 0, fp, fp, nullptr));                        // n_ch > G
+    REFUSED(aggf_gb_regmat_cols_pbc(p, 0, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, nullptr, 0, p, 1, nullptr));
+    REFUSED(aggf_gb_regmat_cols_pbc(p, 0, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, p, 2, p, 1, nullptr));
+    REFUSED(aggf_gb_regmat_cols_pbc(p, 0, p, p, 5, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, p, 3, p, 1, nullptr));
+    REFUSED(aggf_gb_regmat_cols_pbc(p, 1, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, p, 3, p, 0, nullptr));  // f64 products, f32 out
+    REFUSED(aggf_gb_regmat_cols_pbc(p, 0, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 7, p, 3, p, 1, nullptr));    // ld_feat
+    REFUSED(aggf_gb_apply_pbc(p, 0, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 37, nullptr, 3, d, nullptr));
+    REFUSED(aggf_gb_apply_pbc(p, 0, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 37, p, 4, d, nullptr));
+    REFUSED(aggf_gb_apply_pbc(p, 3, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 37, p, 3, d, nullptr));
+    REFUSED(aggf_gb_apply_pbc(p, 0, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 36, p, 3, d, nullptr));  // n_feat
+    REFUSED(aggf_gb_apply_cols_pbc(p, 0, p, p, 0, 10, 5, 2, fp, 5, d, i32, i32, d, p, 8, 1.0, 1e-5, nullptr, 0, d, nullptr));
+    REFUSED(aggf_gb_apply_cols_pbc(p, 0, p, p, 0, 10, 5, 2, fp, 5, d, i32, i32, d, p, 8, 1.0, 1e-5, p, 1, d, nullptr));
+    REFUSED(aggf_gb_apply_cols_pbc(p, 0, p, p, 2, 10, 5, 2, fp, 5, d, i32, i32, d, p, 8, 1.0, 1e-5, p, 3, d, nullptr));
+    REFUSED(aggf_gb_apply_cols_pbc(p, 0, p, p, 0, 10, 5, 2, fp, 5, nullptr, i32, i32, d, p, 8, 1.0, 1e-5, p, 3, d, nullptr));  // id block missing
+    for (int32_t bs : {0, 3}) {
+      RUNS(aggf_gb_distance_range_pbc(fp, fp, 10, 5, 2, 4, fp, bs, fp, fp, nullptr));
+      for (int gd = 0; gd < 2; ++gd) {
+        RUNS(aggf_gb_channels_pbc(p, p, gd, 10, 5, 2, 1, fp, 4, p, 10, 1.0, 1e-3, p, bs, p, p, nullptr));
+        for (int fd = 0; fd < 2; ++fd) {
+          RUNS(aggf_gb_regmat_cols_pbc(p, fd, p, p, gd, 10, 5, 2, 1, fp, 5, i32, 3, p, 10, 1.0, 1e-3, 0.6, 128, p, bs, p, 1, nullptr));
+          RUNS(aggf_gb_apply_pbc(p, fd, p, p, gd, 10, 5, 2, fp, 5, 4, p, 10, 1.0, 1e-3, d, 45, p, bs, d, nullptr));
+          RUNS(aggf_gb_apply_cols_pbc(p, fd, p, p, gd, 10, 5, 2, fp, 5, d, i32, i32, d, p, 10, 1.0, 1e-3, p, bs, d, nullptr));
+        }
+      }
+      RUNS(aggf_gb_regmat_cols_pbc(p, 0, p, p, 0, 10, 5, 2, 1, fp, 5, i32, 3, p, 10, 1.0, 1e-3, 0.6, 128, p, bs, p, 0, nullptr));
+    }
+  }
   REFUSED(aggf_trjdot_frames(nullptr, 1, p, 1, 10, 5, 2, nullptr, p, 1, nullptr));
   REFUSED(aggf_feat_contract(nullptr, 0, p, p, 0, 1.0, 10, 5, 7, 128, p, 1, nullptr));
   REFUSED(aggf_feat_constraint_rows(nullptr, 0, 10, 5, 7, (int64_t*)p, 3, d, 2, 0, d, d, nullptr));

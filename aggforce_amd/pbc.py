@@ -20,9 +20,15 @@ wider type and narrowed, which can differ from the kernel's single rounding in t
 same integers).
 
 Bonds must be shorter than half the box in every component for the minimum image to be the bonded image; that is
-not checked.  Out of scope: triclinic cells, unwrapping across time (jumps between frames), minimum-image distances
-inside ``gb_feat`` (it measures open distances: right within whole molecules smaller than half the cell, still wrong
-between molecules), ``aggforce_amd.stream`` for host trajectories.
+not checked.  Distances BETWEEN molecules are the featuriser's part: ``gb_feat(..., box=)`` measures minimum-image
+distances from a mapped site to the (whole) constraint groups, and takes its box through its own binding::
+
+    project_forces(coords, forces, cmap, box=B, bonds=bonds, method=qp_feat_linear_map,
+                   featurizer=Multifeaturize([id_feat, Curry(gb_feat, outer=..., box=B)]), ...)
+
+Its group means and mapped sites are plain averages: they are right because ``bonds=`` made the groups and beads whole.
+Out of scope: triclinic cells, unwrapping across time (jumps between frames), minimum-image group means,
+``aggforce_amd.stream`` for host trajectories.
 """
 from __future__ import annotations
 

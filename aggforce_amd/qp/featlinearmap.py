@@ -320,11 +320,16 @@ def qp_feat_linear_map(
             )
         coefs.append(X[0].cpu().numpy())
         del feat_dev, div_dev, r3, G
+    # CLAMap's constructor probes the map with ONE frame of zeros; a featuriser that binds a per-frame box
+    # (gb_feat(box=) of shape (n_frames, 3)) takes trajectories of exactly its own length, so the probe is left out
+    from .gbfeat import _per_frame, bound_box
+
     force_map = _feat_linear_mapping(
         featurizer=featurizer,
         coefs=coefs,
         mapping=coord_map,
         constraints=constraints,
+        zeroes_check=not _per_frame(bound_box(featurizer)),
         tags={"feat_names": names, "coef_list": coefs, "constraint_frames": used_frames},
     )
     return CLAFTMap(coord_map=coord_map, force_map=force_map)

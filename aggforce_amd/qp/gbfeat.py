@@ -23,6 +23,14 @@ Reference quirk kept by default (``drop_last_channel=True``): the reference allo
 last-labelled constraint group gets no Gaussian features (Quirk A).  Labels are
 the reference's own, order included (``constraint_group_labels`` reproduces id_feat's labels
 bit for bit), so the group that loses its features is the one the reference drops.
+
+Periodic systems (``box=``, not in the reference): the distance from a mapped site to a group mean is
+the minimum-image distance under an orthorhombic cell, (3,) or one row per frame, and the divergence
+points along the minimum-image displacement (box forms of the K4 kernels).  Bound in the featuriser --
+``Curry(gb_feat, outer=..., box=B)`` -- the box goes through the fused fit, the one-pass
+cross-validation ((3,) only) and the fitted map's application.  The box reaches that one displacement
+and nothing else: group means and mapped sites are plain averages of the coordinates as given, so
+constraint groups and beads must be whole (``pbc.make_whole``, ``project_forces(..., bonds=)``).
 """
 from typing import List, Optional, Tuple
 
@@ -58,9 +66,13 @@ class _Geometry:
     """Device-side per-trajectory quantities shared by all cg sites."""
 
     def __init__(self, coords, cmap: LinearMap, constraints: Constraints, drop_last_channel: bool,
-                 feature_dtype=np.float32):
+                 feature_dtype=np.float32, box=None):
         import torch
 
+        if box is not None:  # shape, and the values of a host box, before any device work
+            from ..jaxutil import _as_box
+
+            box = _as_box(box, coords.shape[0])
         self.fdt = K.torch_dtype(_feature_dtype(feature_dtype))
         self.ids = constraint_group_labels(cmap.n_fg_sites, constraints)
         self.G = int(self.ids.max()) + 1
@@ -79,6 +91,8 @@ class _Geometry:
         # JAX arrays unless feature_dtype=np.float64 was asked for
         self.Pg = K.group_reduce(c, self.grp_ptr, self.grp_atoms, self.G, True, self.fdt)
         self.cg = K.as_device(cmap(c)).to(self.fdt).contiguous()
+        # the cell, (3,) or (T, 3), in the feature dtype beside them (None: open distances)
+        self.box = None if box is None else box.to(device=self.dev, dtype=self.fdt).contiguous()
         # group-summed coordinate map: sum_a M[c,a] [label(a) == g]
         M = np.asarray(cmap.standard_matrix, dtype=np.float64)
         self.Mg = np.add.reduceat(M[:, order], ptr[:-1], axis=1) if self.G < M.shape[1] else M[:, order]
@@ -102,6 +116,7 @@ def gb_feat(
     div_method: str = DIVMETHOD_REORDER,
     drop_last_channel: bool = True,
     feature_dtype=np.float32,
+    box=None,
 ):
     """Featurise each site by its distance to every mapped site (reference jaxfeat.py:20-184).
 
@@ -112,19 +127,27 @@ def gb_feat(
     counterpart) is the arithmetic type of positions, distances and Gaussians: float32 is the
     reference's (JAX default) and the default; float64 evaluates the same expressions in double
     precision (the featurised fit amplifies float32 rounding of the features).
+
+    ``box`` (no reference counterpart): the lengths of an orthorhombic periodic cell, (3,) or (n_frames, 3) for the
+    frames of ``points`` (``ValueError`` otherwise; a host box must be positive and finite, a box on the GPU with a bad
+    length turns its frame's features into NaN; a box that requires a gradient is refused).  The distance from the
+    mapped site to a group mean is then the minimum-image distance, d - L rint(d / L) per component, evaluated in the
+    feature dtype, and the divergence points along that displacement.  Nothing else is wrapped: the group means and
+    the mapped sites ``cmap(points)`` are plain averages of ``points``, so every constraint group and every bead must
+    be whole -- what ``pbc.make_whole`` / ``project_forces(..., bonds=)`` deliver.  Triclinic cells are not built.
     """
     import torch
 
     if div_method not in (DIVMETHOD_REORDER, DIVMETHOD_BASIC):
         raise ValueError("Unknown method for jacobian calculation.")
     fdt = _feature_dtype(feature_dtype)
-    geo = _Geometry(points, cmap, constraints, drop_last_channel, fdt)
+    geo = _Geometry(points, cmap, constraints, drop_last_channel, fdt, box)
     centers = torch.from_numpy(gb_centers(outer, inner, n_basis, dist_power, fdt)).to(geo.dev)
     ids_dev = torch.from_numpy(geo.ids.astype(np.int64)).to(geo.dev)
     keep = torch.nonzero(ids_dev < geo.n_ch).flatten()
 
     def site_arrays(site: int):
-        gauss, grad = K.gb_channels(geo.Pg, geo.cg, site, geo.sizes, geo.n_ch, centers, width, CLIP)
+        gauss, grad = K.gb_channels(geo.Pg, geo.cg, site, geo.sizes, geo.n_ch, centers, width, CLIP, box=geo.box)
         feats = torch.zeros((geo.T, cmap.n_fg_sites, geo.n_ch, n_basis), dtype=geo.fdt, device=geo.dev)
         if keep.numel():
             feats[:, keep, ids_dev[keep], :] = gauss[:, ids_dev[keep], :]
@@ -159,7 +182,7 @@ def _bound_gb_kwargs(f) -> Optional[dict]:
         return None
     kw = dict(getattr(f, "kwargs", None) or getattr(f, "keywords", None) or {})
     allowed = {"outer", "inner", "n_basis", "width", "dist_power", "batch_size", "lazy", "div_method",
-               "drop_last_channel", "feature_dtype"}
+               "drop_last_channel", "feature_dtype", "box"}
     if "outer" not in kw or not set(kw) <= allowed:
         return None
     return kw
@@ -176,6 +199,22 @@ def recognise(featurizers) -> Optional[Tuple[bool, Optional[dict]]]:
     if len(fs) == 2 and fs[0] is id_feat:
         kw = _bound_gb_kwargs(fs[1])
         return (True, kw) if kw is not None else None
+    return None
+
+
+def _per_frame(box) -> bool:
+    """Whether a box as a caller gives it has one row per frame (anything two-dimensional; ``_as_box`` judges it)."""
+    return box is not None and len(getattr(box, "shape", None) or np.shape(box)) == 2
+
+
+def bound_box(featurizer):
+    """The box bound in the gb_feat member of a featuriser -- a ``Multifeaturize`` of the recognised lists or a bound
+    ``gb_feat`` itself -- else None."""
+    members = getattr(featurizer, "featurizers", None)
+    for f in ([featurizer] if members is None else list(members)):
+        kw = _bound_gb_kwargs(f)
+        if kw is not None and kw.get("box") is not None:
+            return kw["box"]
     return None
 
 
@@ -247,7 +286,7 @@ def _fused_setup(coords, forces, coord_map: LinearMap, constraints: Constraints,
     kw = dict(gb_kwargs or {})
     drop_last = kw.pop("drop_last_channel", True)
     fdt = _feature_dtype(kw.pop("feature_dtype", np.float32))
-    geo = _Geometry(coords, coord_map, constraints, drop_last, fdt)
+    geo = _Geometry(coords, coord_map, constraints, drop_last, fdt, kw.pop("box", None))
     n_basis = int(kw.get("n_basis", 10)) if gb_kwargs is not None else 1
     width = float(kw.get("width", 1.0))
     centers_h = (gb_centers(kw["outer"], kw.get("inner", 0), n_basis, kw.get("dist_power", 0.5), fdt)
@@ -267,10 +306,11 @@ def _fused_setup(coords, forces, coord_map: LinearMap, constraints: Constraints,
     # frame (of every rank).  Such a column adds a zero row/column to P and zeros to A: its coefficient in
     # the minimiser is exactly 0, so it is left out (for a cut-off basis most columns are: BASELINE config 4
     # keeps ~2100 of 6139).  The distance range per (site, channel) is a superset test -- it can only keep
-    # columns that are zero after all, never drop one that is not.
+    # columns that are zero after all, never drop one that is not.  Under a box it is the range of the minimum-image
+    # distances, none of which exceeds half the cell's diagonal: fewer columns can be kept, never more.
     keep = np.ones((n_cg, n_ch * n_basis), dtype=bool)
     if n_ch and COMPACT_ZERO_COLUMNS:
-        rmin, rmax = K.gb_distance_range(geo.Pg, geo.cg, n_ch)
+        rmin, rmax = K.gb_distance_range(geo.Pg, geo.cg, n_ch, box=geo.box)
         all_reduce_minmax_(rmin, rmax, comm)
         lo = rmin.cpu().numpy()[:, :n_ch].astype(np.float64)
         hi = rmax.cpu().numpy()[:, :n_ch].astype(np.float64)
@@ -324,9 +364,17 @@ def fit_id_gb(
     gb_kwargs: Optional[dict],
     dense_featurizer,
 ) -> CLAFTMap:
-    """qp_feat_linear_map (featlinearmap.py:249-394) for id_feat and/or gb_feat features, fused."""
+    """qp_feat_linear_map (featlinearmap.py:249-394) for id_feat and/or gb_feat features, fused.  A box bound in the
+    featuriser (``gb_feat(box=)``) goes to every kernel that measures the distance; one row per frame is for the frames
+    of ``traj``, and the fitted map then applies to trajectories of exactly that many frames."""
     import torch
 
+    box_given = (gb_kwargs or {}).get("box")
+    if comm is not None and _per_frame(box_given):
+        # (a rank holds a slice of the frames and would need the matching rows, and the sampled constraint frames
+        # theirs from the rank that owns them: not built.  A (3,) box needs nothing exchanged.)
+        raise ValueError("gb_feat: a per-frame box is not supported with comm= (frames sharded over ranks); bind a "
+                         "(3,) box or fit on one rank")
     su = _fused_setup(traj.coords, traj.forces, coord_map, constraints, use_id, gb_kwargs, comm)
     geo, fdt, drop_last, n_basis, width, centers_h, centers = (su.geo, su.fdt, su.drop_last, su.n_basis, su.width,
                                                                 su.centers_h, su.centers)
@@ -347,6 +395,9 @@ def fit_id_gb(
     flat_idx = np.concatenate(used) if used else np.zeros(0, dtype=np.int64)
     Pg_sel = take_global_frames(geo.Pg, flat_idx, comm)
     cg_sel = take_global_frames(geo.cg, flat_idx, comm)
+    box = geo.box
+    per_frame = box is not None and box.dim() == 2
+    box_sel = box[torch.as_tensor(flat_idx, device=geo.dev)] if per_frame else box  # the sampled frames' own rows
     sel_begin = np.concatenate([[0], np.cumsum([len(u) for u in used])]).astype(np.int64)
     n_sel = {len(u) for u in used}
     n_max = max(n_act)
@@ -404,7 +455,7 @@ def fit_id_gb(
             R3 = R3s[j % n_str]
             cols = cols_dev[site]
             na = n_act[site]
-            K.gb_regmat_cols(Fg, geo.Pg, geo.cg, site, geo.sizes, n_id, cols, centers, width, CLIP, kbt, R3)
+            K.gb_regmat_cols(Fg, geo.Pg, geo.cg, site, geo.sizes, n_id, cols, centers, width, CLIP, kbt, R3, box=box)
             # float64 products: with float32 products the Gram's rounding noise (~1e-7 of its largest entry)
             # exceeds l2 = 10 relative to force-squared sums of ~1e8 and P is no longer numerically positive
             # definite; the exact Gram of the float32 regression matrix always is
@@ -431,7 +482,8 @@ def fit_id_gb(
             gauss = None
             if n_ch:
                 gauss, _ = K.gb_channels(Pg_sel[lo_s:hi_s].contiguous(), cg_sel[lo_s:hi_s].contiguous(), site,
-                                         geo.sizes, n_ch, centers, width, CLIP)
+                                         geo.sizes, n_ch, centers, width, CLIP,
+                                         box=box_sel[lo_s:hi_s].contiguous() if per_frame else box_sel)
             # (the constraint kernels stay inside the site loop: issued for all sites ahead of it they run alone,
             # 5 ms per step at BASELINE config 4 -- here they fill the tails of the Gram launches)
             K.gb_constraint_rows(Mg, gauss, S, n_id, n_ch, n_basis, site, out_A=As[j], out_b=bs[j], cols=cols)  # K4b
@@ -479,16 +531,20 @@ def fit_id_gb(
         return (to(coef_h[:, :n_id]) if n_id else None, to(ptr_h), to(np.concatenate(cols_of)), to(vals))
 
     def apply_f(points, copoints):
-        g2 = _Geometry(copoints, coord_map, constraints, drop_last, fdt)
+        if _per_frame(box_given) and len(box_given) != copoints.shape[0]:
+            raise ValueError(f"this map was fitted with a per-frame box of {len(box_given)} frames and applies to "
+                             f"coordinates of exactly {len(box_given)} frames; got {copoints.shape[0]} (bind a (3,) box "
+                             "in gb_feat to apply a map to other trajectories)")
+        g2 = _Geometry(copoints, coord_map, constraints, drop_last, fdt, box_given)
         key = str(g2.dev)
         if key not in compact:
             compact[key] = compact_on(g2.dev) if sparse else torch.from_numpy(coef_h).to(g2.dev)
         if sparse:
             out = K.gb_apply_cols(g2.group_forces(points), g2.Pg, g2.cg, g2.sizes, n_id, centers.to(g2.dev), width, CLIP,
-                                  compact[key])
+                                  compact[key], box=g2.box)
         else:
             out = K.gb_apply(g2.group_forces(points), g2.Pg, g2.cg, g2.sizes, n_id, n_ch, centers.to(g2.dev), width, CLIP,
-                             compact[key])
+                             compact[key], box=g2.box)
         return K.like_input(out, points)
 
     from .featlinearmap import _feat_linear_mapping
@@ -519,10 +575,16 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
     kept are those not identically zero over ALL frames, a superset of every training set's (their extra coefficients
     are exact zeros: needs l2 > 0, which the caller checks).
 
+    A (3,) box bound in the featuriser is passed through to every kernel; a per-frame box is refused (the frames are
+    gathered into fold order here and the loop's training subsets cannot carry it: ``project_forces_grid_cv`` says so
+    up front).
+
     Returns ``scores[i][k]`` for l2_values[i] and fold k (None where the solve failed, as the loop would skip it), or
     None -- before anything is drawn from ``rng`` -- when the per-fold matrices would not fit the device."""
     import torch
 
+    if _per_frame((gb_kwargs or {}).get("box")):
+        raise ValueError("gb_feat: a per-frame box is not supported in cross-validation; bind a (3,) box")
     n_folds = len(folds)
     lens = [len(f) for f in folds]
     bounds = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -557,7 +619,7 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
         per_alpha = []
         for alpha in ((float(kbt),) if same else (float(kbt), 1.0)):
             K.gb_regmat_cols(su.Fg, geo.Pg, geo.cg, site, geo.sizes, n_id, cols_dev[site], su.centers, su.width, CLIP,
-                             alpha, R3)
+                             alpha, R3, box=geo.box)
             Gf = torch.empty((n_folds, na, na), dtype=torch.float64, device=dev)
             for k in range(n_folds):
                 lead = lead_n if (shared_lead[k] is not None and na >= 256) else 0
@@ -605,7 +667,7 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
                     gauss = None
                     if n_ch:
                         gauss, _ = K.gb_channels(Pg_sel[site * S:(site + 1) * S], cg_sel[site * S:(site + 1) * S], site,
-                                                 geo.sizes, n_ch, su.centers, su.width, CLIP)
+                                                 geo.sizes, n_ch, su.centers, su.width, CLIP, box=geo.box)
                     K.gb_constraint_rows(su.Mg, gauss, S, n_id, n_ch, n_basis, site, out_A=As[j], out_b=bs[j],
                                          cols=cols_dev[site])
                     K.gb_constraint_gram(su.M2, gauss, S, n_id, n_ch, n_basis, AtAs[j], cols=cols_dev[site])

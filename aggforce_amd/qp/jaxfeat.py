@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import _kernels as K
-from ..jaxutil import distances, trjdot
+from ..jaxutil import _as_box, _wrap, distances, distances_in_box, trjdot
 from .gbfeat import gb_centers, gb_feat
 
 __all__ = ["gb_feat", "clipped_gauss", "gaussian_dist_basis", "channel_allocate", "gb_subfeat", "gb_subfeat_jac"]
@@ -135,14 +135,16 @@ def _basis_kwargs(outer, inner=0, n_basis=10, width=1.0, dist_power=0.5, clip=1e
     return outer, inner, n_basis, width, dist_power, clip
 
 
-def _site_distances(points, cg_points, smear_mat):
-    """(smeared points, first cg site (T, 1, 3), their distances (T, N))."""
+def _site_distances(points, cg_points, smear_mat, box=None):
+    """(smeared points, first cg site (T, 1, 3), their distances (T, N)); under ``box`` the minimum-image distances."""
     if smear_mat is not None:
         if isinstance(points, torch.Tensor) and not isinstance(smear_mat, torch.Tensor):
             smear_mat = _tensor(smear_mat, points).to(_tensor(points).dtype)  # (a NumPy constant takes the tensor's dtype)
         points = trjdot(points, smear_mat)
     p = _tensor(points)
     cg = _tensor(cg_points, p)[:, :1, :]
+    if box is not None:
+        return p, cg, distances_in_box(p, box, cross_xyz=cg)[:, 0, :]
     return p, cg, distances(xyz=p, cross_xyz=cg)[:, 0, :]
 
 
@@ -153,12 +155,17 @@ def gb_subfeat(points, cg_points, channels, max_channels, smear_mat, collapse=Fa
 
     (n_frames, n_sites, n_features), (n_features,) collapsed; 2-D ``points`` get and lose a dummy frame axis.  GPU
     tensors are differentiable to any order in ``points``, ``cg_points`` and ``smear_mat``; the channelised form is
-    written by one kernel and the collapsed one summed by one, without the one-hot array."""
+    written by one kernel and the collapsed one summed by one, without the one-hot array.
+
+    ``box`` (a keyword among ``kwargs``, so that the signature stays the reference's; not in the reference; (3,) or
+    (n_frames, 3), a constant; default None): the distances are minimum-image distances under
+    that orthorhombic cell (``jaxutil.distances_in_box``), as ``gb_feat(box=)`` measures them."""
+    box = kwargs.pop("box", None)
     outer, inner, n_basis, width, dist_power, clip = _basis_kwargs(**kwargs)
     dummy_axis = len(points.shape) == 2
     if dummy_axis:
         points = points[None, ...]
-    _, _, r = _site_distances(points, cg_points, smear_mat)
+    _, _, r = _site_distances(points, cg_points, smear_mat, box)
     centers = _grid(r.dtype, outer, inner, n_basis, dist_power)
     if _on_kernels(r):
         from .._autograd import Basis
@@ -187,11 +194,13 @@ def gb_subfeat_jac(points, cg_points, channels, max_channels, smear_mat=None, me
         ``method="basic"``    div[t,(ch,k),:] = sum_{a': ch(a') = ch} (sum_a S[a',a]) W[t,a',k,:]
 
     over the channels below ``max_channels``.  At r = 0 the weight is 0 (the reference gives NaN).  Differentiable as
-    ``gb_subfeat`` is."""
+    ``gb_subfeat`` is.  ``box`` (a keyword among ``kwargs``, as in ``gb_subfeat``): u is the minimum-image displacement u - L rint(u / L) and r its
+    length."""
     if method not in (DIVMETHOD_BASIC, DIVMETHOD_REORDER):
         raise ValueError("Unknown method for jacobian calculation.")
+    box = kwargs.pop("box", None)
     outer, inner, n_basis, width, dist_power, clip = _basis_kwargs(**kwargs)
-    p, cg, r = _site_distances(points, cg_points, smear_mat)
+    p, cg, r = _site_distances(points, cg_points, smear_mat, box)
     centers = _grid(r.dtype, outer, inner, n_basis, dist_power)
     if _on_kernels(r):
         from .._autograd import Basis
@@ -200,7 +209,8 @@ def gb_subfeat_jac(points, cg_points, channels, max_channels, smear_mat=None, me
     else:
         slope = _plain_basis(r, centers, width, clip, q=1)
     pos = r > 0
-    unit = torch.where(pos[..., None], (p - cg) / torch.where(pos, r, torch.ones_like(r))[..., None],
+    disp = p - cg if box is None else _wrap(p - cg, _as_box(box, p.shape[0]))  # (rint is locally constant: no gradient)
+    unit = torch.where(pos[..., None], disp / torch.where(pos, r, torch.ones_like(r))[..., None],
                        torch.zeros_like(p))
     weights = slope[..., None] * unit[:, :, None, :]                            # (T, N, n_basis, 3)
     n_frames, n_sites, nb = slope.shape

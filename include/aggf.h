@@ -396,6 +396,38 @@ int aggf_gb_apply_cols(const void* Fg, int f_dtype, const void* Pg, const void* 
                        const void* centers, int32_t n_basis, double width, double clip, double* out,
                        void* stream);
 
+/* Box forms of the five K4 entry points that measure the distance (not in the reference): the same arguments, launch
+ * plans and guarantees with `box` before the outputs: the lengths of an orthorhombic cell per frame, (T, 3) with
+ * box_stride 3 or one (3,) for all frames with box_stride 0, in g_dtype (float32 for aggf_gb_distance_range_pbc).
+ * Every component of Pg[t,ch] - cg[t,site] is replaced by its minimum image d - L rint(d / L) (the rounding of the
+ * other box kernels: k = rint(d (1/L)), fma(-k, L, d)), so r is the minimum-image distance, u its direction and the
+ * range that of the minimum-image distances.  Pg and cg are taken as given (group means and mapped sites of WHOLE
+ * groups and beads).  A frame with a box length that is not positive and finite has NaN Gaussian features (gauss,
+ * grad, the Gaussian columns of R3, its rows of `out`) and marks every channel as spanning all distances; other
+ * frames are not touched.  NULL box or another stride: AGGF_ERR_ARG.  aggf_gb_regmat has no box form. */
+int aggf_gb_channels_pbc(const void* Pg, const void* cg, int g_dtype, int64_t T, int32_t G, int32_t n_cg,
+                         int32_t site, const float* sizes, int32_t n_ch, const void* centers,
+                         int32_t n_basis, double width, double clip, const void* box, int32_t box_stride,
+                         void* gauss, void* grad, void* stream);
+int aggf_gb_distance_range_pbc(const float* Pg, const float* cg, int64_t T, int32_t G, int32_t n_cg,
+                               int32_t n_ch, const float* box, int32_t box_stride, float* rmin, float* rmax,
+                               void* stream);
+int aggf_gb_regmat_cols_pbc(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                            int32_t G, int32_t n_cg, int32_t site, const float* sizes, int32_t n_id,
+                            const int32_t* cols, int32_t n_cols, const void* centers, int32_t n_basis,
+                            double width, double clip, double kbt, int32_t ld_feat, const void* box,
+                            int32_t box_stride, void* R3, int out_dtype, void* stream);
+int aggf_gb_apply_pbc(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                      int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, int32_t n_ch,
+                      const void* centers, int32_t n_basis, double width, double clip,
+                      const double* coef, int32_t n_feat, const void* box, int32_t box_stride, double* out,
+                      void* stream);
+int aggf_gb_apply_cols_pbc(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                           int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, const double* coef_id,
+                           const int32_t* col_ptr, const int32_t* col_idx, const double* col_val,
+                           const void* centers, int32_t n_basis, double width, double clip, const void* box,
+                           int32_t box_stride, double* out, void* stream);
+
 /* ---------------------------------------------------------------------------
  * K3c  trjdot with a per-frame (3-D) factor.
  *
