@@ -356,6 +356,7 @@ def slice_gather(points: torch.Tensor, idx: torch.Tensor, out_dtype: torch.dtype
 
 
 _flag_pool: dict = {}
+_side_streams: dict = {}
 
 
 def take_flag(device) -> torch.Tensor:
@@ -368,11 +369,16 @@ def take_flag(device) -> torch.Tensor:
     kernel has actually set them, so the steady state issues no fill at all."""
     pool = _flag_pool.setdefault(str(device), [])
     if not pool:
-        block = torch.zeros(64, dtype=torch.int32, device=device)
-        # The fill runs on whatever stream is current (in a fresh process: the side stream of the coordinate gather,
-        # behind a multi-millisecond kernel) while the flags are then used on any stream: wait for it here, once per
-        # 64 flags, so that no later kernel's mark can be wiped by -- or read before -- the fill.
-        torch.cuda.current_stream(block.device).synchronize()
+        # The flags are used on any stream, so their fill must be over before the first one is handed out.  It runs
+        # on a stream of the pool's own and only THAT stream is waited for, once per 64 flags: the caller's current
+        # stream (which may sit behind a long kernel) is never waited for here.
+        key = (str(device), "flags")
+        st = _side_streams.get(key)
+        if st is None:
+            st = _side_streams[key] = torch.cuda.Stream(device=device)
+        with torch.cuda.stream(st):
+            block = torch.zeros(64, dtype=torch.int32, device=device)
+        st.synchronize()
         pool.extend(block[i:i + 1] for i in range(64))
     return pool.pop()
 
@@ -398,9 +404,6 @@ def nan_flag(x: torch.Tensor) -> torch.Tensor:
     if x.numel():
         check(lib().aggf_has_nan(ptr(x), x.numel(), dtype_code(x.dtype), ptr(flag), stream_ptr()), "aggf_has_nan")
     return flag
-
-
-_side_streams: dict = {}
 
 
 def side_stream(device) -> "torch.cuda.Stream":
@@ -664,8 +667,18 @@ def sym_group_reduce(G: torch.Tensor, grp_ptr: torch.Tensor, grp_atoms: torch.Te
 # ------------------------------------------------------------------ synthetic data
 
 
+def index_to_device(host: np.ndarray, device) -> torch.Tensor:
+    """A host index array as a device tensor WITHOUT waiting for the caller's stream: staged in pinned memory and copied
+    asynchronously on the current stream.  (``torch.from_numpy(host).to(device)`` copies from pageable memory and
+    returns only when the current stream has drained: behind a long kernel of the caller's the host stood still.)"""
+    staged = torch.from_numpy(np.ascontiguousarray(host)).pin_memory()
+    return staged.to(device, non_blocking=True)  # (the pinned block is not reused before this copy has run)
+
+
 def take_frames(x: torch.Tensor, idx) -> torch.Tensor:
-    """x[idx] along the frame axis as one gather kernel (aggf_take_frames); ``idx``: integer array-like or tensor."""
+    """x[idx] along the frame axis as one gather kernel (aggf_take_frames); ``idx``: integer array-like or tensor.
+    A host index is checked on the host and the call does not wait for the stream; an index tensor on the DEVICE is
+    range-checked on the host too, which waits for the current stream once."""
     x = x.contiguous()
     n_src = x.shape[0]
     if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
@@ -676,7 +689,7 @@ def take_frames(x: torch.Tensor, idx) -> torch.Tensor:
             raise IndexError(f"frame index out of range for {n_src} frames")
         if host.size and host.min() < 0:
             host = np.where(host < 0, host + n_src, host)
-        idx = torch.from_numpy(np.ascontiguousarray(host)).to(x.device)
+        idx = index_to_device(host, x.device)
     else:
         idx = idx.to(dtype=torch.int64).contiguous()
         lo, hi = (int(v) for v in torch.stack([idx.min(), idx.max()]).tolist()) if idx.numel() else (0, 0)  # one sync
@@ -941,7 +954,7 @@ def feat_constraint_rows(feat: torch.Tensor, frame_idx: np.ndarray, M: torch.Ten
     idx = np.where(idx < 0, idx + T, idx)
     n_cg = M.shape[0]
     S = idx.size
-    idx_dev = torch.from_numpy(idx).to(feat.device)
+    idx_dev = index_to_device(idx, feat.device)
     A = torch.empty((S * n_cg, n_feat), dtype=torch.float64, device=feat.device)
     b = torch.empty((S * n_cg, 1), dtype=torch.float64, device=feat.device)
     check(lib().aggf_feat_constraint_rows(ptr(feat), dtype_code(feat.dtype), T, N, n_feat, ptr(idx_dev), S, ptr(M), n_cg,

@@ -2,8 +2,10 @@
 // expansion) and the counter-based synthetic trajectory generator.
 #include <cxxabi.h>
 #include <dlfcn.h>
+#include <fcntl.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <unistd.h>
 
 #include <atomic>
 
@@ -105,10 +107,17 @@ struct CoverAtExit {
     if (need == 0) return;
     std::string text(need + 1, '\0');
     cover_dump(&text[0], need + 1, label ? label : "-");
-    FILE* f = fopen(path, "a");  // O_APPEND: one write per process, whole lines
-    if (!f) return;
-    fwrite(text.data(), 1, need, f);
-    fclose(f);
+    // O_APPEND and ONE write(2) per process: whole lines even when several child processes exit at once (stdio cut
+    // the text at a buffer boundary into two writes, between which another process's table could land mid-line)
+    const int fd = open(path, O_WRONLY | O_APPEND | O_CREAT, 0644);
+    if (fd < 0) return;
+    size_t done = 0;
+    while (done < need) {  // (a regular file takes it whole; the loop is for a short write only)
+      const ssize_t w = write(fd, text.data() + done, need - done);
+      if (w <= 0) break;
+      done += (size_t)w;
+    }
+    close(fd);
   }
 };
 static CoverAtExit g_cover_at_exit;

@@ -99,6 +99,9 @@ class _ChunkUploader:
         self.ready = [torch.cuda.Event() for _ in range(2)]
         self.free = [torch.cuda.Event() for _ in range(2)]
         self.copy_stream = torch.cuda.Stream(device=device)
+        # the device buffers come from the allocator's pool of the caller's current stream: a block it hands out again may
+        # still be read by work queued there, so the uploads start behind everything already on that stream
+        self.copy_stream.wait_stream(torch.cuda.current_stream(device))
         self._n = 0
 
     def stage(self, begin: int, end: int):
