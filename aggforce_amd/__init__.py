@@ -19,7 +19,7 @@ from .qp import (
     stagedjforcegauss_map,
 )
 from .map import LinearMap
-from .pbc import MoleculeTree, make_whole
+from .pbc import Cell, MoleculeTree, make_whole
 
 __version__ = "0.1.0"
 
@@ -34,6 +34,7 @@ __all__ = [
     "stagedjslicegauss_map",
     "stagedjforcegauss_map",
     "LinearMap",
+    "Cell",
     "MoleculeTree",
     "make_whole",
 ]

@@ -1069,10 +1069,11 @@ def feat_weights(feat: torch.Tensor, coef: torch.Tensor, out: torch.Tensor, site
 def pair_dist_var(x: torch.Tensor, box: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(N, N) float64 population variance over frames of every pair distance; see aggf_pair_dist_var.  ``box`` ((3,)
     or (T, 3), x's dtype and device): the distances are those of the minimum image under that orthorhombic box
-    (aggf_pair_dist_var_pbc); a frame whose box is bad makes every off-diagonal element NaN."""
+    (aggf_pair_dist_var_pbc); a frame whose box is bad makes every off-diagonal element NaN.  (T, 9): the rows of a
+    triclinic cell (``pbc.Cell.rows``), the brick image."""
     l = lib()
     T, N, _ = x.shape
-    stride = None if box is None else _box_arg("pair_dist_var", box, x)
+    stride = None if box is None else _box_arg("pair_dist_var", box, x, cell=True)
     var = torch.empty((N, N), dtype=torch.float64, device=x.device)
     need = l.aggf_pair_dist_var_workspace_bytes(T, N)
     ws = workspace(need, x.device, "pairs")
@@ -1091,7 +1092,7 @@ def pair_dist_moments(x: torch.Tensor, box: Optional[torch.Tensor] = None):
     ``pair_dist_var`` (aggf_pair_dist_moments_pbc)."""
     l = lib()
     T, N, _ = x.shape
-    stride = None if box is None else _box_arg("pair_dist_moments", box, x)
+    stride = None if box is None else _box_arg("pair_dist_moments", box, x, cell=True)
     mean = torch.empty((N, N), dtype=torch.float64, device=x.device)
     var = torch.empty((N, N), dtype=torch.float64, device=x.device)
     need = l.aggf_pair_dist_var_workspace_bytes(T, N)
@@ -1319,16 +1320,19 @@ def _pair_list_sites(name: str, x: torch.Tensor, c: torch.Tensor, tab: PairTable
     return T, m, n, tab.n_pairs
 
 
-def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor) -> int:
-    """The element stride between the frames of ``box``: 3 for (T, 3), 0 for (3,); a contiguous tensor in the dtype
-    and on the device of ``x``."""
+def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor, cell: bool = False) -> int:
+    """The element stride between the frames of ``box`` (the ``box_stride`` of include/aggf.h): 3 for (T, 3), 0 for
+    (3,); a contiguous tensor in the dtype and on the device of ``x``.  ``cell``: the entry also takes (T, 9), a
+    row-major 3 x 3 triclinic cell per frame (``pbc.Cell.rows``), stride 9; the K4 entries do not."""
     T = x.shape[0]
+    shapes = ((3,), (T, 3), (T, 9)) if cell else ((3,), (T, 3))
     if (not isinstance(box, torch.Tensor) or box.dtype != x.dtype or box.device != x.device or not box.is_contiguous()
-            or tuple(box.shape) not in ((3,), (T, 3))):
-        raise ValueError(f"{name}: box must be a contiguous {x.dtype} tensor of shape (3,) or ({T}, 3) on {x.device}; "
+            or tuple(box.shape) not in shapes):
+        raise ValueError(f"{name}: box must be a contiguous {x.dtype} tensor of shape (3,) or ({T}, 3)"
+                         f"{f' or ({T}, 9)' if cell else ''} on {x.device}; "
                          f"got {tuple(box.shape) if hasattr(box, 'shape') else type(box)} "
                          f"{getattr(box, 'dtype', '')} on {getattr(box, 'device', '')}")
-    return 3 if box.dim() == 2 else 0
+    return int(box.shape[1]) if box.dim() == 2 else 0
 
 
 def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int = PAIR_DIST,
@@ -1336,9 +1340,10 @@ def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int 
                    box: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(T, P) in the operands' dtype over u[t,p] = x[t,j_p] - c[t,i_p] (aggf_pair_list_dist): |u|, u.u or
     (v[t,j_p] - y[t,i_p]).u by ``mode``, as ``pair_dist``.  ``box`` ((3,) or (T, 3), the operands' dtype): u is its
-    minimum image under that orthorhombic box (aggf_pair_list_dist_pbc); v - y is never wrapped."""
+    minimum image under that orthorhombic box (aggf_pair_list_dist_pbc); v - y is never wrapped.  (T, 9): the rows of
+    a triclinic cell (``pbc.Cell.rows``), u is its brick image."""
     T, m, n, P = _pair_list_sites("pair_list_dist", x, c, tab)
-    stride = None if box is None else _box_arg("pair_list_dist", box, x)
+    stride = None if box is None else _box_arg("pair_list_dist", box, x, cell=True)
     if mode not in (PAIR_DIST, PAIR_SQDIST, PAIR_DOT):
         raise ValueError(f"pair_list_dist: mode {mode}")
     if mode == PAIR_DOT:
@@ -1368,7 +1373,7 @@ def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairT
     (aggf_pair_list_pull).  An output that is not wanted is None and costs nothing.  All operands share a dtype at
     least as wide as out_dtype (default: theirs).  ``box``: as ``pair_list_dist`` (aggf_pair_list_pull_pbc)."""
     T, m, n, P = _pair_list_sites("pair_list_pull", x, c, tab)
-    stride = None if box is None else _box_arg("pair_list_pull", box, x)
+    stride = None if box is None else _box_arg("pair_list_pull", box, x, cell=True)
     out_dtype = out_dtype or x.dtype
     for name, arr in (("w", w), ("dv", dv)):
         if arr is not None and (tuple(arr.shape) != (T, P) or arr.dtype != x.dtype or not arr.is_contiguous()):
@@ -1402,7 +1407,7 @@ def pair_min(x: torch.Tensor, c: torch.Tensor, square: bool = False, box: Option
     under ``box`` if given (aggf_pair_min, K9e).  A NaN distance makes its pair NaN; without frames every minimum is
     +inf (the empty minimum)."""
     T, m, n = _pair_sites("pair_min", x, c)
-    stride = 0 if box is None else _box_arg("pair_min", box, x)
+    stride = 0 if box is None else _box_arg("pair_min", box, x, cell=True)
     if T == 0:
         return torch.full((m, n), float("inf"), dtype=x.dtype, device=x.device)
     out = torch.empty((m, n), dtype=x.dtype, device=x.device)
@@ -1438,13 +1443,14 @@ def whole_lds_max_sites() -> int:
 
 def make_whole(x: torch.Tensor, box: torch.Tensor, tree: TreeTables, out: Optional[torch.Tensor] = None,
                images: Optional[torch.Tensor] = None, _form: int = WHOLE_AUTO) -> torch.Tensor:
-    """(T, N, 3): x with every molecule of ``tree`` made whole under ``box`` ((3,) or (T, 3), x's dtype), K11
+    """(T, N, 3): x with every molecule of ``tree`` made whole under ``box`` ((3,) or (T, 3), or the (T, 9) rows of a
+    triclinic cell; x's dtype), K11
     (aggf_make_whole).  ``out``: where to write (x itself: in place; default a new tensor); ``images``: a (T, N, 3)
     int32 tensor that receives the image counts.  ``_form`` (tests, benchmarks): WHOLE_LDS or WHOLE_GLOBAL instead of
     the library's choice."""
     if x.dim() != 3 or x.shape[2] != 3 or x.dtype not in (torch.float32, torch.float64) or not x.is_contiguous():
         raise ValueError(f"make_whole: x {tuple(x.shape)} {x.dtype} must be a contiguous (T, N, 3) float32/float64 tensor")
-    stride = _box_arg("make_whole", box, x)
+    stride = _box_arg("make_whole", box, x, cell=True)
     T, N = int(x.shape[0]), int(x.shape[1])
     if N != tree.n or tree.parent.device != x.device:
         raise ValueError(f"make_whole: a tree over {tree.n} atoms on {tree.parent.device} with x {tuple(x.shape)} on "
@@ -1463,7 +1469,8 @@ def make_whole(x: torch.Tensor, box: torch.Tensor, tree: TreeTables, out: Option
     l = lib()
     code = dtype_code(x.dtype)
     jumps = tree.jumps if tree.rounds else None
-    in_lds = _form == WHOLE_LDS or (_form == WHOLE_AUTO and N <= whole_lds_max_sites())
+    # (a triclinic frame stages nine numbers in LDS where a box stages six: the LDS form takes one atom fewer)
+    in_lds = _form == WHOLE_LDS or (_form == WHOLE_AUTO and N <= whole_lds_max_sites() - (1 if stride == 9 else 0))
     # frames per call: all of them, or what keeps the global form's counts within _WHOLE_WS_BYTES
     step = T if in_lds else max(1, min(T, _WHOLE_WS_BYTES // max(1, l.aggf_make_whole_workspace_bytes(1, N, tree.rounds, code))))
     need = 0 if in_lds else l.aggf_make_whole_workspace_bytes(step, N, tree.rounds, code)

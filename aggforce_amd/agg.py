@@ -12,6 +12,7 @@ from typing import Any, Callable, Collection, Dict, Final, List, Mapping, NamedT
 import numpy as np
 
 from . import _kernels as K
+from ._cell import Cell
 from .constraints import Constraints, guess_pairwise_constraints
 from .distributed import (all_reduce_sum_, all_reduce_sum_sym_, cancel_overlap, overlap_with_next_collective,
                           world_size)
@@ -64,11 +65,17 @@ def _mean_square(sumsq, count: int, comm=None) -> float:
     return float(s / n) if n else float("nan")
 
 
-def _checked_box(box, n_steps: int):
+def _checked_box(box, n_steps: int, who: str = "project_forces", comm=None):
     """``box`` as ``jaxutil._as_box`` normalises it: shape (3,) or (n_steps, 3) (ValueError otherwise), host values
-    checked, no device work."""
+    checked, no device work.  A ``pbc.Cell`` (a triclinic cell) is returned as it is once its number of frames is
+    checked; with ``comm`` it is refused: ``who`` names the function."""
     from .jaxutil import _as_box
 
+    if isinstance(box, Cell):
+        if comm is not None:
+            raise ValueError(f"{who}: triclinic cells are not built with comm= (frames sharded over ranks)")
+        box.rows(int(n_steps))
+        return box
     return _as_box(box, int(n_steps))
 
 
@@ -117,7 +124,9 @@ def project_forces(
     (n_steps, 3), for coordinates that are wrapped into it.  It is used by the "auto" guess alone, which then
     measures minimum-image distances (``guess_pairwise_constraints(..., box=)``) and so keeps the rigid pairs
     that straddle a face of the cell in some frames; with explicit constraints or None its shape is checked and
-    it is otherwise ignored.  On its own it changes nothing else: mapped coordinates are still ``coord_map``
+    it is otherwise ignored.  A ``pbc.Cell`` stands for a triclinic cell (brick images, exact up to
+    ``Cell.safe_radius``: ``pbc``), here and in ``bonds``; with ``comm=`` a ``Cell`` is refused.  On its own it
+    changes nothing else: mapped coordinates are still ``coord_map``
     applied to the coordinates as given -- exact for slice maps, off by a box length for averaging maps of
     molecules that the wrap has split (pass ``bonds``) -- and a featuriser gets its box through its own binding
     (``gb_feat(box=)``, below), not from here.
@@ -142,6 +151,8 @@ def project_forces(
     Returns a dict with keys mapped_coords, mapped_forces, tmap, residual, constraints.
     """
     given_coords = coords
+    if isinstance(box, Cell):  # (one with comm= is refused before any device work)
+        _checked_box(box, forces.shape[0], "project_forces", kwargs.get("comm"))
     if bonds is not None:
         coords = _whole_coords(coords, box, bonds)
     if isinstance(constrained_inds, str) and constrained_inds == PROJECT_FORCES_CNSTR_AUTO:
@@ -401,7 +412,7 @@ def project_forces_grid_cv(
     if bonds is not None:
         coords = _whole_coords(coords, box, bonds)
     if box is not None:
-        box = _checked_box(box, n_frames)
+        box = _checked_box(box, n_frames, "project_forces_grid_cv", kwargs.get("comm"))
     frames = np.arange(n_frames)
     (np.random.default_rng() if rng is None else rng).shuffle(frames)
     folds = np.array_split(frames, n_folds)
@@ -449,7 +460,10 @@ def project_forces_grid_cv(
         for k, val_idx in enumerate(folds):
             train_idx = np.concatenate([f for j, f in enumerate(folds) if j != k])
             if box is not None:
-                merged["box"] = box if box.dim() == 1 else box[torch.as_tensor(train_idx, device=box.device)]
+                if isinstance(box, Cell):  # (its training frames, or itself)
+                    merged["box"] = box.take(train_idx)
+                else:
+                    merged["box"] = box if box.dim() == 1 else box[torch.as_tensor(train_idx, device=box.device)]
             try:
                 tmap = project_forces(coords=take(coords, train_idx), forces=take(forces, train_idx), **merged)[
                     TMAP_KNAME

@@ -37,10 +37,20 @@ def guess_pairwise_constraints(xyz, cross_xyz: Union[None, np.ndarray] = None, t
     a face in some frames is still found; without it such a pair's distance jumps by a box length and the
     pair is silently dropped.  Shape and host values are checked before any device work; a box on a GPU is
     checked there.  Lengths that are not positive and finite raise ValueError.
+
+    ``box`` may be a ``pbc.Cell`` (a triclinic cell): every distance is then that of the brick image (``pbc``), in
+    float64 on the triclinic form of K6 -- the minimum-image distance for pairs closer than ``cell.safe_radius``,
+    which every rigid pair of a molecule is.  A cell with a bad frame raises ValueError, as bad lengths do; with
+    ``comm`` a ``Cell`` is refused (not built).
     """
     lengths = None
     if box is not None:
-        from ..jaxutil import _as_box
+        from .._cell import Cell, cell_good, is_cell_rows
+        from ..jaxutil import _as_box, _wrap
+
+        if isinstance(box, Cell) and comm is not None:
+            raise ValueError("guess_pairwise_constraints: triclinic cells are not built with comm= (frames sharded "
+                             "over ranks); guess on one rank")
 
         lengths = _as_box(box, int(xyz.shape[0]) if hasattr(xyz, "shape") else len(xyz))
     if cross_xyz is not None:
@@ -50,10 +60,18 @@ def guess_pairwise_constraints(xyz, cross_xyz: Union[None, np.ndarray] = None, t
             dist = distances(x, cross_xyz=c)
         else:
             disp = distances(x, cross_xyz=c, return_displacements=True).astype(np.float64)
-            L = _host_lengths(lengths)
-            if not (np.isfinite(L) & (L > 0)).all():  # (a box that came from a GPU)
-                raise ValueError("box lengths must be positive and finite")
-            disp = disp - L * np.rint(disp / L)
+            if is_cell_rows(lengths):
+                import torch
+
+                rows = lengths.detach().cpu().double()
+                if not bool(cell_good(rows).all()):  # (a cell that came from a GPU)
+                    raise ValueError("the cell's diagonal must be positive and finite, its lower triangle finite")
+                disp = _wrap(torch.from_numpy(disp), rows).numpy()
+            else:
+                L = _host_lengths(lengths)
+                if not (np.isfinite(L) & (L > 0)).all():  # (a box that came from a GPU)
+                    raise ValueError("box lengths must be positive and finite")
+                disp = disp - L * np.rint(disp / L)
             dist = np.sqrt(np.sum(disp * disp, axis=-1))
         spread = np.std(dist, axis=0)
         first, second = np.nonzero(spread < threshold)
@@ -68,7 +86,10 @@ def guess_pairwise_constraints(xyz, cross_xyz: Union[None, np.ndarray] = None, t
         on_device = lengths.is_cuda
         lengths = lengths.to(device=x.device, dtype=x.dtype).contiguous()
         # (a box that was on the host is checked already; this function synchronises for its result anyway)
-        if on_device and not bool((torch.isfinite(lengths) & (lengths > 0)).all()):
+        if on_device and is_cell_rows(lengths):
+            if not bool(cell_good(lengths).all()):
+                raise ValueError("the cell's diagonal must be positive and finite, its lower triangle finite")
+        elif on_device and not bool((torch.isfinite(lengths) & (lengths > 0)).all()):
             raise ValueError("box lengths must be positive and finite")
     if world_size(comm) > 1:
         # exact pooling of the per-rank (n_r, mean_r, var_r):  var = sum_r (n_r / n) (var_r + (mean_r - mean)^2)

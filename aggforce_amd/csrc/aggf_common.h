@@ -230,6 +230,58 @@ __device__ __forceinline__ bool box_lengths(const T* __restrict__ box, T L[3], T
   return ok;
 }
 
+// ---- triclinic cells.  A cell is three lattice vectors as rows a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) of a
+// lower-triangular matrix (the GROMACS / MDTraj convention), ax, by, cz > 0.  The image of a displacement is obtained
+// by BRICK REDUCTION, each line on the updated d, with min_image's roundings:
+//   kc = rint(dz (1/cz));  dz = fma(-kc, cz, dz);  dy = fma(-kc, cy, dy);  dx = fma(-kc, cx, dx)
+//   kb = rint(dy (1/by));  dy = fma(-kb, by, dy);  dx = fma(-kb, bx, dx)
+//   ka = rint(dx (1/ax));  dx = fma(-ka, ax, dx)
+// the unique lattice translate of d inside the brick |dx| <= ax/2, |dy| <= by/2, |dz| <= cz/2 -- the true minimum
+// image wherever that is shorter than min(ax, by, cz) / 2, a periodic image that is never shorter than it beyond.
+// With zero off-diagonal entries it is min_image component by component, bit for bit (fma(-k, 0, d) == d).
+template <typename T>
+struct CellFrame {
+  T ax, bx, by, cx, cy, cz;  // the six lower-triangular entries
+  T iax, iby, icz;           // 1 / ax, 1 / by, 1 / cz
+};
+__device__ __forceinline__ float cell_rint(float q) { return __builtin_rintf(q); }
+__device__ __forceinline__ double cell_rint(double q) { return __builtin_rint(q); }
+__device__ __forceinline__ float cell_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double cell_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// One frame's cell from its row-major 3 x 3 matrix (nine values of TIn, of which the six lower-triangular ones are
+// read), widened to T.  box_lengths' convention: a diagonal entry that is not positive and finite, or an off-diagonal
+// one that is not finite, makes all nine numbers NaN (and with them everything of that frame); returns whether the
+// cell is good.
+template <typename TIn>
+__device__ __forceinline__ bool cell_good(const TIn* __restrict__ m) {
+  const TIn inf = (TIn)__builtin_inf();
+  return m[0] > (TIn)0 && m[0] < inf && m[4] > (TIn)0 && m[4] < inf && m[8] > (TIn)0 && m[8] < inf &&
+         __builtin_fabs(m[3]) < inf && __builtin_fabs(m[6]) < inf && __builtin_fabs(m[7]) < inf;
+}
+template <typename T, typename TIn>
+__device__ __forceinline__ bool cell_frame(const TIn* __restrict__ m, CellFrame<T>& h) {
+  const T ax = (T)m[0], bx = (T)m[3], by = (T)m[4], cx = (T)m[6], cy = (T)m[7], cz = (T)m[8];
+  const bool ok = cell_good(m);
+  const T nan = (T)__builtin_nan("");
+  h.ax = ok ? ax : nan, h.bx = ok ? bx : nan, h.by = ok ? by : nan;
+  h.cx = ok ? cx : nan, h.cy = ok ? cy : nan, h.cz = ok ? cz : nan;
+  h.iax = (T)1 / h.ax, h.iby = (T)1 / h.by, h.icz = (T)1 / h.cz;
+  return ok;
+}
+// brick reduction of (d0, d1, d2) in place
+template <typename T>
+__device__ __forceinline__ void brick_image(T& d0, T& d1, T& d2, const CellFrame<T>& h) {
+#pragma clang fp contract(off)
+  const T kc = cell_rint(d2 * h.icz);
+  d2 = cell_fma(-kc, h.cz, d2), d1 = cell_fma(-kc, h.cy, d1), d0 = cell_fma(-kc, h.cx, d0);
+  const T kb = cell_rint(d1 * h.iby);
+  d1 = cell_fma(-kb, h.by, d1), d0 = cell_fma(-kb, h.bx, d0);
+  const T ka = cell_rint(d0 * h.iax);
+  d0 = cell_fma(-ka, h.ax, d0);
+}
+// the form of a kernel body: no box, an orthorhombic box (min_image), a triclinic cell (brick_image)
+constexpr int CELL_OPEN = 0, CELL_BOX = 1, CELL_TRI = 2;
+
 // ---- Philox4x32-10 (Salmon et al., SC'11): counter = 64-bit quad index, key = seed ----
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;

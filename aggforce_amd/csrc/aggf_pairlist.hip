@@ -33,7 +33,7 @@ constexpr int64_t PL_TARGET_TASKS = 16384;
 // PBC: u is wrapped to its minimum image under the frame's box (min_image; `box` (T, 3) with bstride 3, or (3,) with
 // bstride 0: a frame's three lengths are wave-uniform and read once per frame, once per task for a constant box).  The
 // tangent operands V - Y of DOT are never wrapped: the wrap is locally constant in X and C.
-template <typename T, int MODE, bool PBC>
+template <typename T, int MODE, int CELL>
 __device__ __forceinline__ void pairlist_body(const T* __restrict__ X, const T* __restrict__ C,
                                               const T* __restrict__ V, const T* __restrict__ Y,
                                               const int32_t* __restrict__ pairs, int64_t nT, int32_t m, int32_t n,
@@ -61,13 +61,18 @@ __device__ __forceinline__ void pairlist_body(const T* __restrict__ X, const T* 
     const T* v = MODE == AGGF_PAIR_DOT ? V + xo : nullptr;
     const T* y = MODE == AGGF_PAIR_DOT ? Y + co : nullptr;
     T L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
-    if (PBC && bstride == 0) box_lengths(box, L, iL);
+    CellFrame<T> h = {};
+    if (CELL == CELL_BOX && bstride == 0) box_lengths(box, L, iL);
 #pragma unroll 4
     for (int64_t t = t0; t < t1; ++t, x += xs, c += cs, o += P) {
       T d0 = x[0] - c[0], d1 = x[1] - c[1], d2 = x[2] - c[2];
-      if (PBC) {
+      if (CELL == CELL_BOX) {
         if (bstride != 0) box_lengths(box + t * bstride, L, iL);
         d0 = min_image(d0, L[0], iL[0]), d1 = min_image(d1, L[1], iL[1]), d2 = min_image(d2, L[2], iL[2]);
+      }
+      if (CELL == CELL_TRI) {
+        cell_frame(box + t * 9, h);
+        brick_image(d0, d1, d2, h);
       }
       T e0 = 0, e1 = 0, e2 = 0;
       if (MODE == AGGF_PAIR_DOT) {
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(256) void pairlist_kernel(const T* __restrict__ X, 
                                                        const T* __restrict__ V, const T* __restrict__ Y,
                                                        const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
                                                        int32_t n, int64_t P, int64_t frames, T* __restrict__ out) {
-  pairlist_body<T, MODE, false>(X, C, V, Y, pairs, nT, m, n, P, frames, nullptr, 0, out);
+  pairlist_body<T, MODE, CELL_OPEN>(X, C, V, Y, pairs, nT, m, n, P, frames, nullptr, 0, out);
 }
 
 template <typename T, int MODE>
@@ -94,7 +99,19 @@ __global__ __launch_bounds__(256) void pairlist_pbc_kernel(const T* __restrict__
                                                            int32_t n, int64_t P, int64_t frames,
                                                            const T* __restrict__ box, int32_t bstride,
                                                            T* __restrict__ out) {
-  pairlist_body<T, MODE, true>(X, C, V, Y, pairs, nT, m, n, P, frames, box, bstride, out);
+  pairlist_body<T, MODE, CELL_BOX>(X, C, V, Y, pairs, nT, m, n, P, frames, box, bstride, out);
+}
+
+// The triclinic form, an overload with a third template argument (CELL_TRI, the only value instantiated): cell is
+// (T, 9), a row-major 3 x 3 cell per frame (brick_image, aggf_common.h).  pairlist_pbc_kernel<T, MODE> is the box form.
+template <typename T, int MODE, int CELL>
+__global__ __launch_bounds__(256) void pairlist_pbc_kernel(const T* __restrict__ X, const T* __restrict__ C,
+                                                           const T* __restrict__ V, const T* __restrict__ Y,
+                                                           const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
+                                                           int32_t n, int64_t P, int64_t frames,
+                                                           const T* __restrict__ cell, T* __restrict__ out) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  pairlist_body<T, MODE, CELL>(X, C, V, Y, pairs, nT, m, n, P, frames, cell, 9, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -125,7 +142,7 @@ __device__ __forceinline__ TI pull_weight(const TI* __restrict__ W, const TI* __
 
 // PBC: Own - Oth is wrapped to its minimum image under the frame's box, as in K9c (min_image is odd, so B is still
 // exactly the sum of -w u); a frame whose box is bad gets NaN sums, sites without entries included.
-template <typename TI, typename TO, bool HAS_DV, int FORM, bool PBC>
+template <typename TI, typename TO, bool HAS_DV, int FORM, int CELL>
 __device__ __forceinline__ void pairlist_pull_body(const TI* __restrict__ W, const TI* __restrict__ Dv,
                                                    const TI* __restrict__ Own, const TI* __restrict__ Oth,
                                                    const int32_t* __restrict__ pairs, int32_t ocol,
@@ -149,7 +166,10 @@ __device__ __forceinline__ void pairlist_pull_body(const TI* __restrict__ W, con
     beg = beg < 0 ? 0 : beg;
     end = end > P ? P : end;
     TI L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
-    const bool box_ok = PBC ? box_lengths(box + t * bstride, L, iL) : true;
+    CellFrame<TI> h = {};
+    const bool box_ok = CELL == CELL_BOX   ? box_lengths(box + t * bstride, L, iL)
+                        : CELL == CELL_TRI ? cell_frame(box + t * 9, h)
+                                           : true;
     const double zero = box_ok ? 0.0 : __builtin_nan("");
     double a0 = zero, a1 = zero, a2 = zero;
     for (int64_t e = FORM == PLP_LANE ? beg : beg + lane; e < end; e += FORM == PLP_LANE ? 1 : 64) {
@@ -160,7 +180,8 @@ __device__ __forceinline__ void pairlist_pull_body(const TI* __restrict__ W, con
       const TI wv = pull_weight<TI, HAS_DV>(w, dv, p);
       const TI* r = oth + 3 * (int64_t)o;
       TI u0 = o0 - r[0], u1 = o1 - r[1], u2 = o2 - r[2];
-      if (PBC) u0 = min_image(u0, L[0], iL[0]), u1 = min_image(u1, L[1], iL[1]), u2 = min_image(u2, L[2], iL[2]);
+      if (CELL == CELL_BOX) u0 = min_image(u0, L[0], iL[0]), u1 = min_image(u1, L[1], iL[1]), u2 = min_image(u2, L[2], iL[2]);
+      if (CELL == CELL_TRI) brick_image(u0, u1, u2, h);
       a0 += (double)(wv * u0), a1 += (double)(wv * u1), a2 += (double)(wv * u2);
     }
     if (FORM == PLP_WAVE) {
@@ -183,7 +204,7 @@ __global__ __launch_bounds__(256) void pairlist_pull_kernel(const TI* __restrict
                                                             const int32_t* __restrict__ ptr,
                                                             const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
                                                             int32_t no, int64_t P, TO* __restrict__ out) {
-  pairlist_pull_body<TI, TO, HAS_DV, FORM, false>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, nullptr, 0, out);
+  pairlist_pull_body<TI, TO, HAS_DV, FORM, CELL_OPEN>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, nullptr, 0, out);
 }
 
 template <typename TI, typename TO, bool HAS_DV, int FORM>
@@ -194,7 +215,20 @@ __global__ __launch_bounds__(256) void pairlist_pull_pbc_kernel(const TI* __rest
                                                                 const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
                                                                 int32_t no, int64_t P, const TI* __restrict__ box,
                                                                 int32_t bstride, TO* __restrict__ out) {
-  pairlist_pull_body<TI, TO, HAS_DV, FORM, true>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box, bstride, out);
+  pairlist_pull_body<TI, TO, HAS_DV, FORM, CELL_BOX>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box, bstride, out);
+}
+
+// (the triclinic form: an overload with a fifth template argument, as pairlist_pbc_kernel's)
+template <typename TI, typename TO, bool HAS_DV, int FORM, int CELL>
+__global__ __launch_bounds__(256) void pairlist_pull_pbc_kernel(const TI* __restrict__ W, const TI* __restrict__ Dv,
+                                                                const TI* __restrict__ Own, const TI* __restrict__ Oth,
+                                                                const int32_t* __restrict__ pairs, int32_t ocol,
+                                                                const int32_t* __restrict__ ptr,
+                                                                const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
+                                                                int32_t no, int64_t P, const TI* __restrict__ cell,
+                                                                TO* __restrict__ out) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  pairlist_pull_body<TI, TO, HAS_DV, FORM, CELL>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, cell, 9, out);
 }
 
 static inline dim3 pairlist_grid(int64_t blocks) {
@@ -221,7 +255,18 @@ static void launch_pairlist(int mode, dim3 grid, hipStream_t stream, const void*
                             const void* Y, const int32_t* pairs, int64_t nT, int32_t m, int32_t n, int64_t P,
                             int64_t frames, const void* box, int32_t bstride, void* out) {
   const dim3 block(256);
-  if (box) {
+  if (box && bstride == 9) {
+#define AGGF_PL_CELL(MODE)                                                                                      \
+  AGGF_LAUNCH((pairlist_pbc_kernel<T, MODE, CELL_TRI>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,   \
+              (const T*)Y, pairs, nT, m, n, P, frames, (const T*)box, (T*)out)
+    if (mode == AGGF_PAIR_DIST)
+      AGGF_PL_CELL(AGGF_PAIR_DIST);
+    else if (mode == AGGF_PAIR_SQDIST)
+      AGGF_PL_CELL(AGGF_PAIR_SQDIST);
+    else
+      AGGF_PL_CELL(AGGF_PAIR_DOT);
+#undef AGGF_PL_CELL
+  } else if (box) {
 #define AGGF_PL_PBC(MODE)                                                                                       \
   AGGF_LAUNCH((pairlist_pbc_kernel<T, MODE>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,    \
               (const T*)Y, pairs, nT, m, n, P, frames, (const T*)box, bstride, (T*)out)
@@ -250,7 +295,15 @@ static void launch_pull_form(int form, hipStream_t stream, const void* W, const 
                              int32_t bstride, void* out) {
   const dim3 block(256);
   const int64_t tasks = nT * ns;
-  if (box && form == PLP_LANE)
+  if (box && bstride == 9 && form == PLP_LANE)
+    AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_LANE, CELL_TRI>), pairlist_grid(ceil_div(tasks, 256)), block, 0,
+                stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
+                P, (const TI*)box, (TO*)out);
+  else if (box && bstride == 9)
+    AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_WAVE, CELL_TRI>), pairlist_grid(ceil_div(tasks, 4)), block, 0,
+                stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
+                P, (const TI*)box, (TO*)out);
+  else if (box && form == PLP_LANE)
     AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_LANE>), pairlist_grid(ceil_div(tasks, 256)), block, 0,
                 stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
                 P, (const TI*)box, bstride, (TO*)out);
@@ -289,10 +342,11 @@ static void launch_pull(int in_dtype, int out_dtype, int32_t max_deg, hipStream_
 #undef AGGF_PULL_FORM
 }
 
-// the box of a box form: (T, 3) or (3,) in the operands' dtype
+// the box of a box form: (T, 3) or (3,) in the operands' dtype, or (T, 9): a triclinic cell per frame
 static int pairlist_box(const char* who, const void* box, int32_t box_stride) {
   if (!box) return fail(AGGF_ERR_ARG, "%s: NULL box", who);
-  if (box_stride != 0 && box_stride != 3) return fail(AGGF_ERR_ARG, "%s: box_stride %d is neither 0 nor 3", who, box_stride);
+  if (box_stride != 0 && box_stride != 3 && box_stride != 9)
+    return fail(AGGF_ERR_ARG, "%s: box_stride %d is none of 0, 3 and 9", who, box_stride);
   return AGGF_OK;
 }
 

@@ -48,11 +48,13 @@ static PairMinPlan pairmin_plan(int64_t T, int32_t m, int32_t n, int dtype) {
 }
 
 // dst: out when the plan has one split (root: the sqrt is applied here), else the (splits, m, n) partials
-template <typename T, bool PBC>
-__global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, const T* __restrict__ C, int64_t nT,
-                                                      int32_t m, int32_t n, int64_t jblocks, int64_t iblocks,
-                                                      int64_t frames, const T* __restrict__ box, int32_t bstride,
-                                                      int root, T* __restrict__ dst) {
+// (one body for the three forms: CELL_OPEN, CELL_BOX -- min_image --, CELL_TRI -- box is (T, 9), a triclinic cell per
+// frame, brick_image)
+template <typename T, int CELL>
+__device__ __forceinline__ void pairmin_body(const T* __restrict__ X, const T* __restrict__ C, int64_t nT, int32_t m,
+                                             int32_t n, int64_t jblocks, int64_t iblocks, int64_t frames,
+                                             const T* __restrict__ box, int32_t bstride, int root,
+                                             T* __restrict__ dst) {
   const int64_t tiles = jblocks * iblocks;
   const int64_t split = (int64_t)blockIdx.x / tiles, tile = (int64_t)blockIdx.x - split * tiles;
   const int64_t ib = tile / jblocks, jb = tile - ib * jblocks;
@@ -70,15 +72,18 @@ __global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, c
   const T* x = X + t0 * xs + 3 * jc;
   const T* c = C + t0 * cs;
   T L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
-  if (PBC && bstride == 0) box_lengths(box, L, iL);
+  CellFrame<T> h = {};
+  if (CELL == CELL_BOX && bstride == 0) box_lengths(box, L, iL);
   for (int64_t t = t0; t < t1; ++t, x += xs, c += cs) {
     const T x0 = x[0], x1 = x[1], x2 = x[2];
-    if (PBC && bstride != 0) box_lengths(box + t * bstride, L, iL);
+    if (CELL == CELL_BOX && bstride != 0) box_lengths(box + t * bstride, L, iL);
+    if (CELL == CELL_TRI) cell_frame(box + t * 9, h);
 #pragma unroll
     for (int r = 0; r < PM_ROWS; ++r) {
       const T* cr = c + coff[r];
       T d0 = x0 - cr[0], d1 = x1 - cr[1], d2 = x2 - cr[2];
-      if (PBC) d0 = min_image(d0, L[0], iL[0]), d1 = min_image(d1, L[1], iL[1]), d2 = min_image(d2, L[2], iL[2]);
+      if (CELL == CELL_BOX) d0 = min_image(d0, L[0], iL[0]), d1 = min_image(d1, L[1], iL[1]), d2 = min_image(d2, L[2], iL[2]);
+      if (CELL == CELL_TRI) brick_image(d0, d1, d2, h);
       acc[r] = nan_min(acc[r], pair_element<T, AGGF_PAIR_SQDIST>(d0, d1, d2, (T)0, (T)0, (T)0));
     }
   }
@@ -87,6 +92,24 @@ __global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, c
 #pragma unroll
   for (int r = 0; r < PM_ROWS; ++r)
     if (i0 + r < m) o[(int64_t)r * n] = root ? sqrt(acc[r]) : acc[r];
+}
+
+template <typename T, bool PBC>
+__global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, const T* __restrict__ C, int64_t nT,
+                                                      int32_t m, int32_t n, int64_t jblocks, int64_t iblocks,
+                                                      int64_t frames, const T* __restrict__ box, int32_t bstride,
+                                                      int root, T* __restrict__ dst) {
+  pairmin_body<T, PBC ? CELL_BOX : CELL_OPEN>(X, C, nT, m, n, jblocks, iblocks, frames, box, bstride, root, dst);
+}
+
+// (the triclinic form: an overload with a third template argument, CELL_TRI the only value instantiated)
+template <typename T, bool PBC, int CELL>
+__global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, const T* __restrict__ C, int64_t nT,
+                                                      int32_t m, int32_t n, int64_t jblocks, int64_t iblocks,
+                                                      int64_t frames, const T* __restrict__ cell, int root,
+                                                      T* __restrict__ dst) {
+  static_assert(PBC && CELL == CELL_TRI, "the triclinic form");
+  pairmin_body<T, CELL>(X, C, nT, m, n, jblocks, iblocks, frames, cell, 9, root, dst);
 }
 
 template <typename T>
@@ -113,7 +136,10 @@ static void launch_pairmin(const PairMinPlan& p, hipStream_t stream, const void*
   const bool split = p.splits > 1;
   const int root = !split && !square;
   T* dst = (T*)(split ? ws : out);
-  if (box)
+  if (box && bstride == 9)
+    AGGF_LAUNCH((pairmin_kernel<T, true, CELL_TRI>), grid, block, 0, stream, (const T*)X, (const T*)C, nT, m, n, p.jblocks,
+                p.iblocks, p.frames, (const T*)box, root, dst);
+  else if (box)
     AGGF_LAUNCH((pairmin_kernel<T, true>), grid, block, 0, stream, (const T*)X, (const T*)C, nT, m, n, p.jblocks,
                 p.iblocks, p.frames, (const T*)box, bstride, root, dst);
   else
@@ -144,8 +170,9 @@ extern "C" int aggf_pair_min(const void* X, const void* C, int64_t T, int32_t m,
   hipStream_t stream = (hipStream_t)stream_v;
   if (T < 0 || m < 0 || n < 0) return fail(AGGF_ERR_ARG, "aggf_pair_min: negative shape");
   if (dtype != AGGF_F32 && dtype != AGGF_F64) return fail(AGGF_ERR_ARG, "aggf_pair_min: bad dtype");
-  if (box_stride != 0 && box_stride != 3)
-    return fail(AGGF_ERR_ARG, "aggf_pair_min: box_stride %d is neither 0 nor 3", box_stride);
+  if (box_stride != 0 && box_stride != 3 && box_stride != 9)
+    return fail(AGGF_ERR_ARG, "aggf_pair_min: box_stride %d is none of 0, 3 and 9", box_stride);
+  if (box_stride == 9 && !box) return fail(AGGF_ERR_ARG, "aggf_pair_min: box_stride 9 without a cell");
   if (T == 0 || m == 0 || n == 0) return AGGF_OK;
   int64_t sites = 0;
   if (__builtin_mul_overflow(T, 3 * (int64_t)(m > n ? m : n), &sites) || sites > INT64_MAX / 8)

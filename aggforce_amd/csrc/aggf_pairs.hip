@@ -38,13 +38,22 @@ __device__ __forceinline__ bool box_lengths_wide(const TIn* __restrict__ box, do
   return box_lengths(b, L, invL);
 }
 
-template <typename TIn, bool PBC>
+// one displacement under the form's cell: L / iL for a box, h for a triclinic cell
+template <int CELL>
+__device__ __forceinline__ void pair_wrap(double& dx, double& dy, double& dz, const double L[3], const double iL[3],
+                                          const CellFrame<double>& h) {
+  if (CELL == CELL_BOX) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+  if (CELL == CELL_TRI) brick_image(dx, dy, dz, h);
+}
+
+template <typename TIn, int CELL>
 __device__ __forceinline__ void pair_stats_body(const TIn* __restrict__ X, int64_t T, int32_t N, int32_t nt1,
                                                 int32_t n_tiles, int64_t frames_per_split,
                                                 const TIn* __restrict__ box, int32_t bstride,
                                                 double* __restrict__ slabs) {
   __shared__ double sp[2][PFB][PT][3];    // [i-block | j-block][frame][atom][xyz]
-  __shared__ double sb[PBC ? PFB : 1][6];  // PBC: [frame][L xyz | 1/L xyz]
+  __shared__ double sb[CELL == CELL_BOX ? PFB : 1][6];          // box: [frame][L xyz | 1/L xyz]
+  __shared__ CellFrame<double> sc[CELL == CELL_TRI ? PFB : 1];  // triclinic: [frame] six entries and three inverses
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
   const int ks = b / n_tiles;
@@ -81,11 +90,13 @@ __device__ __forceinline__ void pair_stats_body(const TIn* __restrict__ X, int64
     for (int x = 0; x < 4; ++x) load_atom(0, ti * PT + bi + x, pi[x]);
     for (int y = 0; y < 4; ++y) load_atom(0, tj * PT + bj + y, pj[y]);
     double L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
-    if (PBC) box_lengths_wide(box, L, iL);  // frame 0's box
+    CellFrame<double> h = {};
+    if (CELL == CELL_BOX) box_lengths_wide(box, L, iL);  // frame 0's box
+    if (CELL == CELL_TRI) cell_frame(box, h);
     for (int x = 0; x < 4; ++x)
       for (int y = 0; y < 4; ++y) {
         double dx = pj[y][0] - pi[x][0], dy = pj[y][1] - pi[x][1], dz = pj[y][2] - pi[x][2];
-        if (PBC) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+        pair_wrap<CELL>(dx, dy, dz, L, iL, h);
         d0[x][y] = pair_norm(dx, dy, dz);
       }
   }
@@ -104,25 +115,28 @@ __device__ __forceinline__ void pair_stats_body(const TIn* __restrict__ X, int64
       if (t < t_end && a < N) v = (double)X[(t * N + a) * 3 + q % 3];
       (&sp[side][f][0][0])[q] = v;
     }
-    if (PBC && tid < PFB) {  // (frames past t_end are staged but never read)
+    if (CELL != CELL_OPEN && tid < PFB) {  // (frames past t_end are staged but never read)
       const int64_t t = t0 + tid;
-      if (t < t_end) box_lengths_wide(box + t * bstride, &sb[tid][0], &sb[tid][3]);
+      if (CELL == CELL_BOX && t < t_end) box_lengths_wide(box + t * bstride, &sb[tid][0], &sb[tid][3]);
+      if (CELL == CELL_TRI && t < t_end) cell_frame(box + t * 9, sc[tid]);
     }
     __syncthreads();
     const int nf = (int)((t_end - t0) < PFB ? (t_end - t0) : PFB);
     for (int f = 0; f < nf; ++f) {
       double L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
-      if (PBC) {
+      CellFrame<double> h = {};
+      if (CELL == CELL_BOX) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) L[k] = sb[f][k], iL[k] = sb[f][3 + k];
       }
+      if (CELL == CELL_TRI) h = sc[f];
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
         const double ax = sp[0][f][bi + x][0], ay = sp[0][f][bi + x][1], az = sp[0][f][bi + x][2];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
           double dx = sp[1][f][bj + y][0] - ax, dy = sp[1][f][bj + y][1] - ay, dz = sp[1][f][bj + y][2] - az;
-          if (PBC) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+          pair_wrap<CELL>(dx, dy, dz, L, iL, h);
           const double dd = pair_norm(dx, dy, dz) - d0[x][y];
           s1[x][y] += dd;
           s2[x][y] = __builtin_fma(dd, dd, s2[x][y]);
@@ -144,7 +158,7 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const TIn* __restrict__
                                                          int32_t nt1, int32_t n_tiles,
                                                          int64_t frames_per_split,
                                                          double* __restrict__ slabs) {
-  pair_stats_body<TIn, false>(X, T, N, nt1, n_tiles, frames_per_split, nullptr, 0, slabs);
+  pair_stats_body<TIn, CELL_OPEN>(X, T, N, nt1, n_tiles, frames_per_split, nullptr, 0, slabs);
 }
 
 template <typename TIn>
@@ -153,13 +167,26 @@ __global__ __launch_bounds__(256) void pair_stats_pbc_kernel(const TIn* __restri
                                                              int64_t frames_per_split,
                                                              const TIn* __restrict__ box, int32_t bstride,
                                                              double* __restrict__ slabs) {
-  pair_stats_body<TIn, true>(X, T, N, nt1, n_tiles, frames_per_split, box, bstride, slabs);
+  pair_stats_body<TIn, CELL_BOX>(X, T, N, nt1, n_tiles, frames_per_split, box, bstride, slabs);
+}
+
+// cell: (T, 9), a row-major 3 x 3 triclinic cell per frame in the coordinates' dtype (brick_image in float64)
+// (two workgroups per CU, the box form's occupancy: without the bound the nine cell numbers take it to one)
+// The triclinic form is an overload with a second template argument (CELL_TRI, the only value instantiated).
+template <typename TIn, int CELL>
+__global__ __launch_bounds__(256, 2) void pair_stats_pbc_kernel(const TIn* __restrict__ X, int64_t T, int32_t N,
+                                                                int32_t nt1, int32_t n_tiles,
+                                                                int64_t frames_per_split,
+                                                                const TIn* __restrict__ cell,
+                                                                double* __restrict__ slabs) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  pair_stats_body<TIn, CELL>(X, T, N, nt1, n_tiles, frames_per_split, cell, 9, slabs);
 }
 
 // var[i,j] (N x N, symmetric, diagonal 0) from the slabs, fixed summation order
 // mean (optional): mean distance over the frames = d0 + shifted mean, d0 recomputed from frame 0 of X (PBC: its
 // minimum image under frame 0's box, as the statistics kernel formed it)
-template <typename TIn, bool PBC>
+template <typename TIn, int CELL>
 __device__ __forceinline__ void pair_var_body(const double* __restrict__ slabs, int32_t nt1, int32_t ksplit,
                                               int32_t N, int64_t T, double* __restrict__ var,
                                               const TIn* __restrict__ X, const TIn* __restrict__ box,
@@ -178,7 +205,9 @@ __device__ __forceinline__ void pair_var_body(const double* __restrict__ slabs, 
   const int tj = ti + tile;
   const double* base = slabs + (int64_t)tile_lin * ksplit * (2 * PT * PT);
   double L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
-  if (PBC && mean) box_lengths_wide(box, L, iL);  // frame 0's box
+  CellFrame<double> h = {};
+  if (CELL == CELL_BOX && mean) box_lengths_wide(box, L, iL);  // frame 0's box
+  if (CELL == CELL_TRI && mean) cell_frame(box, h);
   for (int e = threadIdx.x; e < PT * PT; e += 256) {
     const int i = ti * PT + e / PT, j = tj * PT + e % PT;
     if (i >= N || j >= N) continue;
@@ -197,7 +226,7 @@ __device__ __forceinline__ void pair_var_body(const double* __restrict__ slabs, 
       double dx = (double)X[(int64_t)j * 3 + 0] - (double)X[(int64_t)i * 3 + 0],
              dy = (double)X[(int64_t)j * 3 + 1] - (double)X[(int64_t)i * 3 + 1],
              dz = (double)X[(int64_t)j * 3 + 2] - (double)X[(int64_t)i * 3 + 2];
-      if (PBC) dx = min_image(dx, L[0], iL[0]), dy = min_image(dy, L[1], iL[1]), dz = min_image(dz, L[2], iL[2]);
+      pair_wrap<CELL>(dx, dy, dz, L, iL, h);
       // (from float64 coordinates the inner product here is ux ux and uy uy the fused one: the form this
       // instantiation has always had)
       const double mu = i == j ? 0.0 : (sizeof(TIn) == 8 ? pair_norm(dy, dx, dz) : pair_norm(dx, dy, dz)) + m;
@@ -212,7 +241,7 @@ __global__ __launch_bounds__(256) void pair_var_kernel(const double* __restrict_
                                                        int32_t ksplit, int32_t N, int64_t T,
                                                        double* __restrict__ var, const TIn* __restrict__ X,
                                                        double* __restrict__ mean) {
-  pair_var_body<TIn, false>(slabs, nt1, ksplit, N, T, var, X, nullptr, mean);
+  pair_var_body<TIn, CELL_OPEN>(slabs, nt1, ksplit, N, T, var, X, nullptr, mean);
 }
 
 template <typename TIn>
@@ -221,7 +250,16 @@ __global__ __launch_bounds__(256) void pair_var_pbc_kernel(const double* __restr
                                                            double* __restrict__ var, const TIn* __restrict__ X,
                                                            const TIn* __restrict__ box,
                                                            double* __restrict__ mean) {
-  pair_var_body<TIn, true>(slabs, nt1, ksplit, N, T, var, X, box, mean);
+  pair_var_body<TIn, CELL_BOX>(slabs, nt1, ksplit, N, T, var, X, box, mean);
+}
+
+template <typename TIn, int CELL>
+__global__ __launch_bounds__(256) void pair_var_pbc_kernel(const double* __restrict__ slabs, int32_t nt1,
+                                                           int32_t ksplit, int32_t N, int64_t T,
+                                                           double* __restrict__ var, const TIn* __restrict__ X,
+                                                           const TIn* __restrict__ cell, double* __restrict__ mean) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  pair_var_body<TIn, CELL>(slabs, nt1, ksplit, N, T, var, X, cell, mean);
 }
 
 // out = weight * (var_r + (mean_r - mean)^2): this rank's term of the pooled variance
@@ -264,7 +302,13 @@ template <typename TIn>
 static int launch_pair_moments(dim3 grid, hipStream_t stream, const void* X, int64_t T, int32_t N, int nt1,
                                int n_tiles, int ksplit, int64_t fps, const void* box, int32_t bstride, double* slabs,
                                double* mean, double* var) {
-  if (box) {
+  if (box && bstride == 9) {
+    AGGF_LAUNCH((pair_stats_pbc_kernel<TIn, CELL_TRI>), grid, dim3(256), 0, stream, (const TIn*)X, T, N, nt1, n_tiles, fps,
+                (const TIn*)box, slabs);
+    AGGF_LAUNCH_OK();
+    AGGF_LAUNCH((pair_var_pbc_kernel<TIn, CELL_TRI>), dim3(n_tiles), dim3(256), 0, stream, slabs, nt1, ksplit, N, T, var,
+                (const TIn*)X, (const TIn*)box, mean);
+  } else if (box) {
     AGGF_LAUNCH(pair_stats_pbc_kernel<TIn>, grid, dim3(256), 0, stream, (const TIn*)X, T, N, nt1, n_tiles, fps,
                 (const TIn*)box, bstride, slabs);
     AGGF_LAUNCH_OK();
@@ -300,10 +344,11 @@ static int pair_moments_impl(const void* X, int64_t T, int32_t N, int dtype, con
   return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
 }
 
-// the box of a box form: (T, 3) or (3,) in the coordinates' dtype
+// the box of a box form: (T, 3) or (3,) in the coordinates' dtype, or (T, 9): a triclinic cell per frame
 static int pair_moments_box(const char* who, const void* box, int32_t box_stride) {
   if (!box) return fail(AGGF_ERR_ARG, "%s: NULL box", who);
-  if (box_stride != 0 && box_stride != 3) return fail(AGGF_ERR_ARG, "%s: box_stride %d is neither 0 nor 3", who, box_stride);
+  if (box_stride != 0 && box_stride != 3 && box_stride != 9)
+    return fail(AGGF_ERR_ARG, "%s: box_stride %d is none of 0, 3 and 9", who, box_stride);
   return AGGF_OK;
 }
 

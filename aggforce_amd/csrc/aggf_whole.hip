@@ -79,6 +79,53 @@ __device__ __forceinline__ T whole_shift(int32_t k, T L, T x) {
   return wh_fma(-(T)k, L, x);
 }
 
+
+// ---- the triclinic forms (whole_lds_kernel<T, CELL_TRI>, whole_edge_kernel<..>, whole_shift_kernel<..>): `box` is (T, 9), a
+// row-major 3 x 3 cell per frame (CellFrame, aggf_common.h).  The edge counts of an atom are the three counts of the
+// brick reduction of x_i - x_parent(i), each treated as the box form treats its one: 0 where q is not finite, clamped
+// to WH_MAX_EDGE, and the next stage reduced with that count:
+//   kc = cnt(dz (1/cz));  dy = fma(-kc, cy, dy);  dx = fma(-kc, cx, dx)
+//   kb = cnt(dy (1/by));  dx = fma(-kb, bx, dx)
+//   ka = cnt(dx (1/ax))
+// Element c of an atom holds the count of lattice vector c (0: a, 1: b, 2: c); the jump rounds sum each as before, and
+//   u = x - kc c - kb b - ka a   as nested fmas in that order, component by component (zero entries skipped).
+// With zero off-diagonal entries every number is the box form's, bit for bit.  A bad cell (cell_frame) is all NaN:
+// counts 0, coordinates NaN.
+template <typename T>
+__device__ __forceinline__ T whole_count(T q) {
+  if (!(__builtin_fabs(q) < (T)__builtin_inf())) return (T)0;
+  const T r = wh_rint(q);
+  return r > (T)WH_MAX_EDGE ? (T)WH_MAX_EDGE : (r < (T)-WH_MAX_EDGE ? (T)-WH_MAX_EDGE : r);
+}
+// the count of lattice vector c for atom i whose parent is p; row: the frame's N x 3 coordinates
+template <typename T>
+__device__ __forceinline__ int32_t whole_edge_cell(const T* row, int32_t i, int32_t p, int32_t c, int32_t N,
+                                                   const CellFrame<T>& h) {
+#pragma clang fp contract(off)
+  if (p == -1) return 0;
+  if (!((uint32_t)p < (uint32_t)N)) return WH_BAD;
+  const T* x = row + 3 * (int64_t)i;
+  const T* xp = row + 3 * (int64_t)p;
+  T d0 = x[0] - xp[0], d1 = x[1] - xp[1];
+  const T d2 = x[2] - xp[2];
+  const T kc = whole_count(d2 * h.icz);
+  d1 = wh_fma(-kc, h.cy, d1), d0 = wh_fma(-kc, h.cx, d0);
+  const T kb = whole_count(d1 * h.iby);
+  d0 = wh_fma(-kb, h.bx, d0);
+  const T ka = whole_count(d0 * h.iax);
+  return (int32_t)(c == 0 ? ka : (c == 1 ? kb : kc));
+}
+// component c of the shifted atom from its three counts and component c of the three lattice vectors (ac: c == 0
+// only, bc: c <= 1 only)
+template <typename T>
+__device__ __forceinline__ T whole_shift_cell(int32_t ka, int32_t kb, int32_t kc, int32_t c, T ac, T bc, T cc, T x) {
+  if (ka == WH_BAD || kb == WH_BAD || kc == WH_BAD) return (T)__builtin_nan("");
+  T u = wh_fma(-(T)kc, cc, x);
+  if (c <= 1) u = wh_fma(-(T)kb, bc, u);
+  if (c == 0) u = wh_fma(-(T)ka, ac, u);
+  return u;
+}
+
 // ---------------------------------------------------------------------------
 // LDS form.  A workgroup of WH_THREADS lanes takes `frames` consecutive frames at a time: a contiguous span of
 // len = frames 3 N elements of X, element g of the span being component c = (g mod 3N) mod 3 of atom i = (g mod 3N) / 3
@@ -113,10 +160,16 @@ static_assert((3 * (int64_t)WH_LDS_MAX_N + 3 + 3) / 4 <= (int64_t)WH_THREADS * (
                   (3 * (int64_t)WH_LDS_MAX_N + 1 + 1) / 2 <= (int64_t)WH_THREADS * (WH_ELEMS / 2),
               "a lane's registers hold the largest frame");
 
-static inline int64_t whole_lds_lengths_bytes(int32_t frames) { return round_up(6 * (int64_t)frames * 8, 16); }
+// A triclinic frame stages nine numbers (CellFrame) where a box stages six: the largest frame of the cell form is one
+// atom smaller, 24 N + 80 <= 163,840 => N <= 6823 (WH_LDS_MAX_N_CELL); nothing else of the plan differs.
+constexpr int32_t WH_LDS_MAX_N_CELL = (WH_LDS_BYTES - 80) / 24;
+static_assert(WH_LDS_MAX_N_CELL == WH_LDS_MAX_N - 1, "the bound derived above");
+static inline int64_t whole_lds_lengths_bytes(int32_t frames, bool cell = false) {
+  return round_up((cell ? 9 : 6) * (int64_t)frames * 8, 16);
+}
 // (a forest without rounds never touches the second count buffer: it is not allocated)
-static inline int64_t whole_lds_bytes(int32_t frames, int32_t N, int32_t rounds) {
-  return whole_lds_lengths_bytes(frames) + (rounds > 0 ? 2 : 1) * 4 * 3 * (int64_t)frames * N;
+static inline int64_t whole_lds_bytes(int32_t frames, int32_t N, int32_t rounds, bool cell = false) {
+  return whole_lds_lengths_bytes(frames, cell) + (rounds > 0 ? 2 : 1) * 4 * 3 * (int64_t)frames * N;
 }
 static int32_t whole_lds_frames(int64_t T, int32_t N) {
   int64_t f = WH_SPAN / (3 * (int64_t)N);
@@ -126,19 +179,19 @@ static int32_t whole_lds_frames(int64_t T, int32_t N) {
   return f < 1 ? 1 : (int32_t)f;
 }
 
-template <typename T>
-__global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64_t nT, int32_t N,
-                                                               const int32_t* __restrict__ parent,
-                                                               const int32_t* __restrict__ jumps, int32_t rounds,
-                                                               const T* __restrict__ box, int32_t bstride,
-                                                               int32_t frames, T* out, int32_t* __restrict__ images) {
+template <typename T, int CELL>
+__device__ __forceinline__ void whole_lds_body(const T* X, int64_t nT, int32_t N, const int32_t* __restrict__ parent,
+                                               const int32_t* __restrict__ jumps, int32_t rounds,
+                                               const T* __restrict__ box, int32_t bstride, int32_t frames, T* out,
+                                               int32_t* __restrict__ images) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   using V = typename Vec16<T>::type;
   constexpr int VN = Vec16<T>::N, SLOTS = WH_ELEMS / VN;
   const int32_t n3 = 3 * N, tid = threadIdx.x;
   T* sL = reinterpret_cast<T*>(smem_raw);
   T* sI = sL + 3 * frames;
-  int32_t* kbuf = reinterpret_cast<int32_t*>(smem_raw + (6 * (int64_t)frames * 8 + 15) / 16 * 16);
+  CellFrame<T>* sH = reinterpret_cast<CellFrame<T>*>(smem_raw);  // (CELL_TRI: instead of sL and sI)
+  int32_t* kbuf = reinterpret_cast<int32_t*>(smem_raw + ((CELL == CELL_TRI ? 9 : 6) * (int64_t)frames * 8 + 15) / 16 * 16);
   const int64_t groups = (nT + frames - 1) / frames;
   for (int64_t grp = blockIdx.x; grp < groups; grp += gridDim.x) {
     const int64_t t0 = grp * frames;
@@ -152,7 +205,8 @@ __global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64
     const bool vec_out = ((uintptr_t)os & 15) == ((uintptr_t)xs & 15);
     int32_t* cur = kbuf;
     int32_t* nxt = kbuf + (int64_t)frames * n3;
-    if (tid < 3 * nf) whole_box_length(box + (t0 + tid / 3) * bstride + tid % 3, sL + tid, sI + tid);
+    if (CELL == CELL_BOX && tid < 3 * nf) whole_box_length(box + (t0 + tid / 3) * bstride + tid % 3, sL + tid, sI + tid);
+    if (CELL == CELL_TRI && tid < nf) cell_frame(box + (t0 + tid) * 9, sH[tid]);
     __syncthreads();
 
     // per owned element: coordinate and meta = atom index | (3 frame + component) << 16; -1: not in the span
@@ -182,7 +236,10 @@ __global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64
         const int32_t g = g0 + q;
         if (g < gs || g >= len) continue;
         meta[s][q] = i | ((3 * f + c) << 16);
-        cur[g] = whole_edge<T>(xs + (int64_t)f * n3, xr[s][q], parent[i], c, N, sI[3 * f + c]);
+        if (CELL == CELL_TRI)
+          cur[g] = whole_edge_cell<T>(xs + (int64_t)f * n3, i, parent[i], c, N, sH[f]);
+        else
+          cur[g] = whole_edge<T>(xs + (int64_t)f * n3, xr[s][q], parent[i], c, N, sI[3 * f + c]);
         if (++c == 3) {
           c = 0;
           if (++i == N) i = 0, ++f;
@@ -217,7 +274,18 @@ __global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64
       if (cell >= ncell) continue;
       T u[VN];
 #pragma unroll
-      for (int q = 0; q < VN; ++q) u[q] = meta[s][q] < 0 ? (T)0 : whole_shift<T>(cur[g0 + q], sL[meta[s][q] >> 16], xr[s][q]);
+      for (int q = 0; q < VN; ++q) {
+        if (meta[s][q] < 0) {
+          u[q] = (T)0;
+        } else if (CELL == CELL_TRI) {
+          const int32_t fc = meta[s][q] >> 16, f = fc / 3, c = fc - 3 * f;
+          const int32_t* k = cur + (g0 + q - c);
+          const T* e = &sH[f].ax;  // ax | bx by | cx cy cz
+          u[q] = whole_shift_cell<T>(k[0], k[1], k[2], c, e[0], e[c <= 1 ? 1 + c : 1], e[3 + c], xr[s][q]);
+        } else {
+          u[q] = whole_shift<T>(cur[g0 + q], sL[meta[s][q] >> 16], xr[s][q]);
+        }
+      }
       if (vec_out && g0 >= 0 && g0 + VN <= len) {
         V v;
 #pragma unroll
@@ -235,6 +303,27 @@ __global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64_t nT, int32_t N,
+                                                               const int32_t* __restrict__ parent,
+                                                               const int32_t* __restrict__ jumps, int32_t rounds,
+                                                               const T* __restrict__ box, int32_t bstride,
+                                                               int32_t frames, T* out, int32_t* __restrict__ images) {
+  whole_lds_body<T, CELL_BOX>(X, nT, N, parent, jumps, rounds, box, bstride, frames, out, images);
+}
+
+// (the triclinic forms of the three kernels are overloads with a second template argument, CELL_TRI the only value
+// instantiated, and no stride among their arguments)
+template <typename T, int CELL>
+__global__ __launch_bounds__(WH_THREADS) void whole_lds_kernel(const T* X, int64_t nT, int32_t N,
+                                                               const int32_t* __restrict__ parent,
+                                                               const int32_t* __restrict__ jumps, int32_t rounds,
+                                                               const T* __restrict__ cell, int32_t frames, T* out,
+                                                               int32_t* __restrict__ images) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  whole_lds_body<T, CELL>(X, nT, N, parent, jumps, rounds, cell, 9, frames, out, images);
+}
+
 // ---------------------------------------------------------------------------
 // Global form: element e of the (T, 3 N) arrays per lane, grid-stride; counts (T, 3 N) int32 in the workspace.
 template <typename T>
@@ -248,6 +337,21 @@ __global__ __launch_bounds__(256) void whole_edge_kernel(const T* __restrict__ X
     T L, iL;
     whole_box_length(box + t * bstride + c, &L, &iL);
     cnt[g] = whole_edge<T>(X + t * n3, X[g], parent[i], c, N, iL);
+  }
+}
+
+template <typename T, int CELL>
+__global__ __launch_bounds__(256) void whole_edge_kernel(const T* __restrict__ X, int64_t nT, int32_t N,
+                                                         const int32_t* __restrict__ parent,
+                                                         const T* __restrict__ cell, int32_t* __restrict__ cnt) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  const int64_t n3 = 3 * (int64_t)N, total = nT * n3;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+    const int64_t t = g / n3;
+    const int32_t e = (int32_t)(g - t * n3), i = e / 3, c = e - 3 * i;
+    CellFrame<T> h;
+    cell_frame(cell + t * 9, h);
+    cnt[g] = whole_edge_cell<T>(X + t * n3, i, parent[i], c, N, h);
   }
 }
 
@@ -278,6 +382,25 @@ __global__ __launch_bounds__(256) void whole_shift_kernel(const T* X, const int3
   }
 }
 
+template <typename T, int CELL>
+__global__ __launch_bounds__(256) void whole_shift_kernel(const T* X, const int32_t* __restrict__ cnt, int64_t nT,
+                                                          int32_t N, const T* __restrict__ cell, T* out,
+                                                          int32_t* __restrict__ images) {
+  static_assert(CELL == CELL_TRI, "the triclinic form");
+  const int64_t n3 = 3 * (int64_t)N, total = nT * n3;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+    const int64_t t = g / n3;
+    const int32_t c = (int32_t)((g - t * n3) % 3);
+    const T* m = cell + t * 9;  // (component c of the rows a, b, c: m[c], m[3 + c], m[6 + c]; no inverse is needed)
+    const T nan = (T)__builtin_nan("");
+    const bool ok = cell_good(m);
+    const int32_t* k = cnt + (g - c);
+    out[g] = whole_shift_cell<T>(k[0], k[1], k[2], c, ok ? m[0] : nan, ok ? m[c <= 1 ? 3 + c : 3] : nan,
+                                 ok ? m[6 + c] : nan, X[g]);
+    if (images) images[g] = k[c];
+  }
+}
+
 // ---------------------------------------------------------------------------
 constexpr int WH_AUTO = 0, WH_LDS = 1, WH_GLOBAL = 2;
 
@@ -298,17 +421,22 @@ template <typename T>
 static int launch_whole_lds(hipStream_t stream, const void* X, int64_t nT, int32_t N, const int32_t* parent,
                             const int32_t* jumps, int32_t rounds, const void* box, int32_t bstride, void* out,
                             int32_t* images) {
-  static PerDeviceOnce once;
-  if (!*once.flag()) {
-    AGGF_HIP_OK(hipFuncSetAttribute((const void*)whole_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    WH_LDS_BYTES));
-    *once.flag() = true;
+  const bool cell = bstride == 9;
+  static PerDeviceOnce once[2];
+  if (!*once[cell].flag()) {
+    AGGF_HIP_OK(hipFuncSetAttribute(cell ? (const void*)whole_lds_kernel<T, CELL_TRI> : (const void*)whole_lds_kernel<T>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS_BYTES));
+    *once[cell].flag() = true;
   }
   const int32_t frames = whole_lds_frames(nT, N);
-  const int64_t lds = whole_lds_bytes(frames, N, rounds);
+  const int64_t lds = whole_lds_bytes(frames, N, rounds, cell);
   if (lds > WH_LDS_BYTES) return fail(AGGF_ERR_ARG, "aggf_make_whole: %d atoms do not fit the LDS form", N);
-  AGGF_LAUNCH((whole_lds_kernel<T>), whole_grid(ceil_div(nT, frames), 1 << 20), dim3(WH_THREADS), (size_t)lds, stream,
-              (const T*)X, nT, N, parent, jumps, rounds, (const T*)box, bstride, frames, (T*)out, images);
+  if (cell)
+    AGGF_LAUNCH((whole_lds_kernel<T, CELL_TRI>), whole_grid(ceil_div(nT, frames), 1 << 20), dim3(WH_THREADS), (size_t)lds,
+                stream, (const T*)X, nT, N, parent, jumps, rounds, (const T*)box, frames, (T*)out, images);
+  else
+    AGGF_LAUNCH((whole_lds_kernel<T>), whole_grid(ceil_div(nT, frames), 1 << 20), dim3(WH_THREADS), (size_t)lds, stream,
+                (const T*)X, nT, N, parent, jumps, rounds, (const T*)box, bstride, frames, (T*)out, images);
   return AGGF_OK;
 }
 
@@ -320,14 +448,22 @@ static void launch_whole_global(hipStream_t stream, const void* X, int64_t nT, i
   const dim3 grid = whole_grid(ceil_div(total, 256), 65536), block(256);
   int32_t* cur = (int32_t*)ws;
   int32_t* nxt = cur + total;
-  AGGF_LAUNCH((whole_edge_kernel<T>), grid, block, 0, stream, (const T*)X, nT, N, parent, (const T*)box, bstride, cur);
+  const bool cell = bstride == 9;
+  if (cell)
+    AGGF_LAUNCH((whole_edge_kernel<T, CELL_TRI>), grid, block, 0, stream, (const T*)X, nT, N, parent, (const T*)box, cur);
+  else
+    AGGF_LAUNCH((whole_edge_kernel<T>), grid, block, 0, stream, (const T*)X, nT, N, parent, (const T*)box, bstride, cur);
   for (int32_t r = 0; r < rounds; ++r) {
     AGGF_LAUNCH(whole_jump_kernel, grid, block, 0, stream, (const int32_t*)cur, jumps + (int64_t)r * N, nT, N, nxt);
     int32_t* sw = cur;
     cur = nxt, nxt = sw;
   }
-  AGGF_LAUNCH((whole_shift_kernel<T>), grid, block, 0, stream, (const T*)X, (const int32_t*)cur, nT, N, (const T*)box,
-              bstride, (T*)out, images);
+  if (cell)
+    AGGF_LAUNCH((whole_shift_kernel<T, CELL_TRI>), grid, block, 0, stream, (const T*)X, (const int32_t*)cur, nT, N,
+                (const T*)box, (T*)out, images);
+  else
+    AGGF_LAUNCH((whole_shift_kernel<T>), grid, block, 0, stream, (const T*)X, (const int32_t*)cur, nT, N, (const T*)box,
+                bstride, (T*)out, images);
 }
 
 }  // namespace aggf
@@ -351,17 +487,18 @@ extern "C" int aggf_make_whole(const void* X, int64_t T, int32_t N, int dtype, c
   if (rounds < 0 || rounds > WH_MAX_ROUNDS)
     return fail(AGGF_ERR_ARG, "aggf_make_whole: %d rounds (a forest of depth 2^16 or more is refused)", rounds);
   if (!box) return fail(AGGF_ERR_ARG, "aggf_make_whole: NULL box");
-  if (box_stride != 0 && box_stride != 3)
-    return fail(AGGF_ERR_ARG, "aggf_make_whole: box_stride %d is neither 0 nor 3", box_stride);
+  if (box_stride != 0 && box_stride != 3 && box_stride != 9)
+    return fail(AGGF_ERR_ARG, "aggf_make_whole: box_stride %d is none of 0, 3 and 9", box_stride);
+  const int32_t lds_max = box_stride == 9 ? WH_LDS_MAX_N_CELL : WH_LDS_MAX_N;
   if (form != WH_AUTO && form != WH_LDS && form != WH_GLOBAL) return fail(AGGF_ERR_ARG, "aggf_make_whole: bad form");
   if (T == 0 || N == 0) return AGGF_OK;
   const int64_t ws_need = whole_ws_bytes(T, N, rounds);
   if (ws_need == 0) return fail(AGGF_ERR_ARG, "aggf_make_whole: T N does not fit a 64-bit byte offset");
   if (!X || !parent || !out) return fail(AGGF_ERR_ARG, "aggf_make_whole: NULL pointer");
   if (rounds > 0 && !jumps) return fail(AGGF_ERR_ARG, "aggf_make_whole: rounds without jump tables");
-  if (form == WH_LDS && N > WH_LDS_MAX_N)
-    return fail(AGGF_ERR_ARG, "aggf_make_whole: the LDS form holds at most %d atoms, not %d", WH_LDS_MAX_N, N);
-  if (form == WH_AUTO) form = N <= WH_LDS_MAX_N ? WH_LDS : WH_GLOBAL;
+  if (form == WH_LDS && N > lds_max)
+    return fail(AGGF_ERR_ARG, "aggf_make_whole: the LDS form holds at most %d atoms, not %d", lds_max, N);
+  if (form == WH_AUTO) form = N <= lds_max ? WH_LDS : WH_GLOBAL;
   if (form == WH_LDS) {
     const int rc = dtype == AGGF_F64 ? launch_whole_lds<double>(stream, X, T, N, parent, jumps, rounds, box, box_stride,
                                                                 out, images)

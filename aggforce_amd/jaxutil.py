@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _kernels as K
+from ._cell import Cell, is_cell_rows
 
 _FACTOR_MSG = "Factor matrix is an incompatible shape."
 
@@ -121,7 +122,13 @@ def _as_box(box, n_steps: int) -> torch.Tensor:
     """``box`` as a tensor of shape (3,) or (n_steps, 3): the lengths of an orthorhombic cell, one for all frames or
     one per frame.  A box on the host (a sequence, a NumPy array, a CPU tensor) is checked here -- positive, finite --
     and comes out as float64; a box on a GPU is taken as it is (no synchronisation: the kernels turn a frame whose
-    box is bad into NaN).  The box is a constant: one that requires a gradient is refused."""
+    box is bad into NaN).  The box is a constant: one that requires a gradient is refused.
+
+    A ``pbc.Cell`` (a triclinic cell, checked when it was made) comes out as its (n_steps, 9) rows -- the row-major
+    matrix of every frame, a constant cell expanded -- which no raw array can be: (n_steps, 9) is refused like every
+    other raw shape."""
+    if isinstance(box, Cell):
+        return box.rows(n_steps).contiguous()
     if isinstance(box, torch.Tensor):
         if box.requires_grad:
             raise ValueError("box is a constant: gradients with respect to box lengths are not built")
@@ -142,8 +149,21 @@ def _as_box(box, n_steps: int) -> torch.Tensor:
 
 
 def _wrap(disp: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
-    """The minimum image of displacements (T, ..., 3) in plain torch: d - L rint(d / L), rint to nearest even."""
+    """The minimum image of displacements (T, ..., 3) in plain torch: d - L rint(d / L), rint to nearest even.  Under
+    the (T, 9) rows of a ``Cell``: its brick reduction (``_cell``) in the same plain operations, stage by stage on
+    the updated displacement -- with zero off-diagonal entries the box form's numbers bit for bit (d - 0 k == d)."""
     L = box.to(device=disp.device, dtype=disp.dtype if disp.dtype.is_floating_point else torch.float64)
+    if is_cell_rows(L):
+        h = L.reshape((L.shape[0],) + (1,) * (disp.dim() - 2) + (9,))
+        ax, bx, by, cx, cy, cz = (h[..., k] for k in (0, 3, 4, 6, 7, 8))
+        d0, d1, d2 = disp[..., 0], disp[..., 1], disp[..., 2]
+        kc = torch.round(d2 / cz)
+        d2, d1, d0 = d2 - cz * kc, d1 - cy * kc, d0 - cx * kc
+        kb = torch.round(d1 / by)
+        d1, d0 = d1 - by * kb, d0 - bx * kb
+        ka = torch.round(d0 / ax)
+        d0 = d0 - ax * ka
+        return torch.stack([d0, d1, d2], dim=-1)
     if L.dim() == 2:
         L = L.reshape((L.shape[0],) + (1,) * (disp.dim() - 2) + (3,))
     return disp - L * torch.round(disp / L)
@@ -234,12 +254,18 @@ class PairList:
         in the order of ``upper_triangle``; the cross form keeps all (i, j) in row-major order.  ``exclude`` (a
         ``PairList`` or a (k, 2) integer array): pairs to leave out, e.g. bonded ones; in the self form (i, j) and
         (j, i) are the same pair.  Under a box the minimum image is only the nearest image up to half a box length:
-        a cutoff beyond half the smallest length of any frame raises ``ValueError``."""
+        a cutoff beyond half the smallest length of any frame raises ``ValueError``.  Under a ``pbc.Cell`` the list
+        is exact for ``cutoff <= cell.safe_radius``: a host cell with a larger cutoff raises ``ValueError``; with a cell
+        on a GPU (not read back) that condition is the caller's part."""
         cutoff = float(cutoff)
         if not cutoff >= 0 or not np.isfinite(cutoff):
             raise ValueError(f"cutoff must be a non-negative finite number; got {cutoff}")
         dmin = min_distances(xyz, cross_xyz, box=box)
-        if box is not None:
+        if isinstance(box, Cell):
+            if not box.is_cuda and not cutoff <= box.safe_radius:
+                raise ValueError(f"cutoff {cutoff} is beyond the cell's safe radius min(ax, by, cz) / 2 = "
+                                 f"{box.safe_radius}: the brick image is not the nearest image there")
+        elif box is not None:
             lengths = _as_box(box, int(xyz.shape[0]) if hasattr(xyz, "shape") else len(xyz)).detach().cpu().double()
             if lengths.numel() and not cutoff <= 0.5 * float(lengths.min()):
                 raise ValueError(f"cutoff {cutoff} is beyond half the smallest box length {float(lengths.min())}: the "
@@ -284,7 +310,10 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False, box=None) -
 
     ``box``: the lengths of an orthorhombic periodic cell, (3,) or (n_steps, 3) (a sequence, an array or a tensor; a
     constant).  Every displacement is then its minimum image, d - L rint(d / L) per component -- the nearest image
-    for distances up to half a box length -- on the box forms of the same kernels."""
+    for distances up to half a box length -- on the box forms of the same kernels.  A ``pbc.Cell`` (a triclinic
+    cell): every displacement is its brick image -- the nearest image for distances up to ``cell.safe_radius``, a
+    periodic image that is never shorter than it beyond -- on the triclinic forms of the same kernels, with every
+    convention of the box forms (inputs, dtypes, gradients of any order, NaN for a bad frame)."""
     def shape_of(a):
         return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
 
@@ -336,6 +365,7 @@ def min_distances(xyz, cross_xyz=None, square: bool = False, box=None) -> torch.
         if len(shape) != 3 or shape[2] != 3:
             raise ValueError(f"sites must have shape (n_steps, n_sites, 3); got {shape}")
     n_steps = int(xyz.shape[0]) if hasattr(xyz, "shape") else len(xyz)
+    given = box
     if box is not None:
         box = _as_box(box, n_steps)
     if _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
@@ -345,7 +375,7 @@ def min_distances(xyz, cross_xyz=None, square: bool = False, box=None) -> torch.
         x, c = x.to(ct).contiguous(), c.to(ct).contiguous()
         return K.pair_min(x, c, bool(square), None if box is None else box.to(device=x.device, dtype=ct).contiguous())
     with torch.no_grad():
-        d = _distances(xyz, cross_xyz, True, False, square, box)
+        d = _distances(xyz, cross_xyz, True, False, square, given)
         if d.shape[0] == 0:
             return torch.full(tuple(d.shape[1:]), float("inf"), dtype=d.dtype, device=d.device)
         return d.amin(dim=0)
@@ -374,8 +404,9 @@ def distances_in_box(
     square: bool = False,
 ) -> torch.Tensor:
     """``distances`` under an orthorhombic periodic cell (not in the reference): minimum-image distances and
-    displacements for ``box`` as in ``pair_distances``.  On GPU tensors both forms run on the pair-list kernels -- the
-    matrix over ``PairList.all_pairs``, reshaped -- since the matrix kernels K9a / K9b have no box form."""
+    displacements for ``box`` as in ``pair_distances`` (the lengths of a box, or a ``pbc.Cell``).  On GPU tensors both
+    forms run on the pair-list kernels -- the matrix over ``PairList.all_pairs``, reshaped -- since the matrix kernels
+    K9a / K9b have no box form."""
     if box is None:
         raise ValueError("distances_in_box needs a box; without one it is distances")
     return _distances(xyz, cross_xyz, return_matrix, return_displacements, square, box)

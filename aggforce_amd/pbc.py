@@ -27,8 +27,21 @@ distances from a mapped site to the (whole) constraint groups, and takes its box
                    featurizer=Multifeaturize([id_feat, Curry(gb_feat, outer=..., box=B)]), ...)
 
 Its group means and mapped sites are plain averages: they are right because ``bonds=`` made the groups and beads whole.
-Out of scope: triclinic cells, unwrapping across time (jumps between frames), minimum-image group means,
-``aggforce_amd.stream`` for host trajectories.
+Triclinic cells: ``box=Cell(vectors)`` (``Cell``, below and ``_cell.py``: three lattice vectors a, b, c as the rows of
+a lower-triangular matrix).  Every function that takes the lengths of a box here takes a ``Cell`` -- ``make_whole``,
+``jaxutil.pair_distances`` / ``distances_in_box`` / ``min_distances``, ``PairList.from_cutoff``,
+``guess_pairwise_constraints``, ``project_forces(..., box=, bonds=)`` and ``project_forces_grid_cv`` -- on the triclinic
+forms of the same kernels.  The image of a displacement is its brick reduction (``_cell``): the true minimum image up to
+``Cell.safe_radius = min(ax, by, cz) / 2``, a periodic image that is never shorter than it beyond.  For ``make_whole``::
+
+    n_i = (ka, kb, kc), the three counts of the brick reduction of x_i - x_parent(i)   (0 for a root)
+    k_i = n_i + the n of all ancestors of i                                            integer triples sum exactly
+    u_i = x_i - kc c - kb b - ka a                                                     nested fmas in that order
+
+and the image counts (T, N, 3) are those of a, b, c in that order.  Bonds must be shorter than ``safe_radius``.
+
+Out of scope: unwrapping across time (jumps between frames), minimum-image group means, ``aggforce_amd.stream`` for
+host trajectories (it takes no box); under a ``Cell`` also ``gb_feat`` (refused) and ``comm=`` (refused).
 """
 from __future__ import annotations
 
@@ -36,6 +49,7 @@ import numpy as np
 import torch
 
 from . import _kernels as K
+from ._cell import Cell, cell_good, is_cell_rows  # noqa: F401  (Cell: part of this module's surface)
 from .jaxutil import PairList, _as_box
 
 MAX_DEPTH = 1 << 16  # a forest this deep is refused: the int32 image counts of K11 cannot overflow below it
@@ -233,13 +247,55 @@ def _host_whole(x: np.ndarray, box: np.ndarray, tree: MoleculeTree):
     return u.reshape(T, N, 3), np.ascontiguousarray(k, dtype=np.int32).reshape(T, N, 3)
 
 
+def _host_whole_cell(x: np.ndarray, rows: np.ndarray, tree: MoleculeTree):
+    """The NumPy body under a triclinic cell: (u, k) for x (T, N, 3) float32/float64 and rows (T, 9) in x's dtype, with
+    the arithmetic of K11's triclinic form (each fma as a product and sum in the next wider type, narrowed once)."""
+    dt = x.dtype.type
+    T, N = x.shape[0], x.shape[1]
+    wide = np.float64 if x.dtype == np.float32 else np.longdouble
+    with np.errstate(all="ignore"):
+        good = cell_good(torch.from_numpy(np.ascontiguousarray(rows))).numpy()
+        h = np.where(good[:, None], rows, dt(np.nan)).astype(x.dtype).reshape(T, 1, 9)
+        ax, bx, by, cx, cy, cz = (h[..., k] for k in (0, 3, 4, 6, 7, 8))
+        iax, iby, icz = dt(1) / ax, dt(1) / by, dt(1) / cz
+        par = tree.parent
+        has = par >= 0
+        d = x - x[:, np.maximum(par, 0)]
+
+        def count(q):
+            r = np.clip(np.rint(q), -_MAX_EDGE, _MAX_EDGE)
+            return np.where(np.isfinite(q), r, 0).astype(x.dtype)
+
+        def fnma(k, c, v):  # fma(-k, c, v), rounded once
+            return (v.astype(wide) - k.astype(wide) * c.astype(wide)).astype(x.dtype)
+
+        d0, d1, d2 = d[..., 0], d[..., 1], d[..., 2]
+        kc = count(d2 * icz)
+        d1, d0 = fnma(kc, cy, d1), fnma(kc, cx, d0)
+        kb = count(d1 * iby)
+        d0 = fnma(kb, bx, d0)
+        ka = count(d0 * iax)
+        n = np.where(has[None, :, None], np.stack([ka, kb, kc], axis=-1), 0).astype(np.int32)
+        k = n
+        for jr in tree.jumps:
+            k = k + np.where((jr >= 0)[None, :, None], k[:, np.maximum(jr, 0)], 0)
+        fa, fb, fc = (k[..., c].astype(x.dtype) for c in range(3))
+        u0 = fnma(fa, ax, fnma(fb, bx, fnma(fc, cx, x[..., 0])))
+        u1 = fnma(fb, by, fnma(fc, cy, x[..., 1]))
+        u2 = fnma(fc, cz, x[..., 2])
+        u = np.stack([u0, u1, u2], axis=-1)
+    return u.reshape(T, N, 3), np.ascontiguousarray(k, dtype=np.int32).reshape(T, N, 3)
+
+
 def make_whole(xyz, box, tree, *, inplace: bool = False, return_images: bool = False):
     """``xyz`` (n_steps, n_sites, 3) with every molecule of ``tree`` made whole under ``box``: each atom at the
     minimum image of its parent in the forest, roots where they are (see the module's text for the arithmetic).
 
     ``box``: the lengths of an orthorhombic cell, (3,) or (n_steps, 3), as everywhere (``jaxutil``): a box on the host
     is checked, a box on a GPU is not -- a length that is not positive and finite makes its frame's coordinates NaN
-    (image counts 0) and no other frame's.  ``tree``: a ``MoleculeTree`` (or bonds: a ``PairList`` / (k, 2) array,
+    (image counts 0) and no other frame's.  A ``Cell``: a triclinic cell -- every atom at the brick image of its
+    parent, the image counts those of a, b, c in that order (the module's text), a bad frame NaN in every
+    component.  ``tree``: a ``MoleculeTree`` (or bonds: a ``PairList`` / (k, 2) array,
     turned into one).  A non-finite coordinate stays where it is and moves nothing else.
 
     NumPy in gives NumPy out, a tensor gives a tensor on its device, in the input's dtype (float32 / float64; anything
@@ -285,7 +341,8 @@ def make_whole(xyz, box, tree, *, inplace: bool = False, return_images: bool = F
             arr = arr.astype(np.float64)
     if inplace and not _float_array(xyz):
         raise ValueError("make_whole: inplace=True needs a float32 or float64 array")
-    u, k = _host_whole(arr, box.detach().cpu().numpy().astype(arr.dtype), tree)
+    host = _host_whole_cell if is_cell_rows(box) else _host_whole
+    u, k = host(arr, box.detach().cpu().numpy().astype(arr.dtype), tree)
     if is_tensor:
         images = torch.from_numpy(k)
         if inplace:

@@ -70,7 +70,10 @@ class _Geometry:
         import torch
 
         if box is not None:  # shape, and the values of a host box, before any device work
+            from .._cell import refuse_cell
             from ..jaxutil import _as_box
+
+            refuse_cell(box, "gb_feat")
 
             box = _as_box(box, coords.shape[0])
         self.fdt = K.torch_dtype(_feature_dtype(feature_dtype))

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .. import _kernels as K
+from .._cell import refuse_cell
 from ..jaxutil import _as_box, _wrap, distances, distances_in_box, trjdot
 from .gbfeat import gb_centers, gb_feat
 
@@ -161,6 +162,7 @@ def gb_subfeat(points, cg_points, channels, max_channels, smear_mat, collapse=Fa
     (n_frames, 3), a constant; default None): the distances are minimum-image distances under
     that orthorhombic cell (``jaxutil.distances_in_box``), as ``gb_feat(box=)`` measures them."""
     box = kwargs.pop("box", None)
+    refuse_cell(box, "gb_subfeat")
     outer, inner, n_basis, width, dist_power, clip = _basis_kwargs(**kwargs)
     dummy_axis = len(points.shape) == 2
     if dummy_axis:
@@ -199,6 +201,7 @@ def gb_subfeat_jac(points, cg_points, channels, max_channels, smear_mat=None, me
     if method not in (DIVMETHOD_BASIC, DIVMETHOD_REORDER):
         raise ValueError("Unknown method for jacobian calculation.")
     box = kwargs.pop("box", None)
+    refuse_cell(box, "gb_subfeat_jac")
     outer, inner, n_basis, width, dist_power, clip = _basis_kwargs(**kwargs)
     p, cg, r = _site_distances(points, cg_points, smear_mat, box)
     centers = _grid(r.dtype, outer, inner, n_basis, dist_power)

@@ -556,11 +556,26 @@ int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void
  * number makes every output of its frame NaN.  Where every |d| is far below L / 2 the results
  * are those of the open entry points bit for bit.
  *
+ * Triclinic cells: box_stride 9 means `box` is (T, 9), a row-major 3 x 3 cell per frame in the
+ * operands' dtype, rows a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) (a constant cell is
+ * expanded by the caller); the six lower-triangular entries alone are read.  u is replaced by its
+ * BRICK REDUCTION, each line on the updated d, inverses formed once per frame:
+ *     kc = rint(dz * (1/cz));  dz = fma(-kc, cz, dz);  dy = fma(-kc, cy, dy);  dx = fma(-kc, cx, dx)
+ *     kb = rint(dy * (1/by));  dy = fma(-kb, by, dy);  dx = fma(-kb, bx, dx)
+ *     ka = rint(dx * (1/ax));  dx = fma(-ka, ax, dx)
+ * the lattice translate of u inside the brick |dx| <= ax/2, |dy| <= by/2, |dz| <= cz/2: the true
+ * minimum image wherever that is shorter than min(ax, by, cz) / 2, a periodic image never shorter
+ * than it beyond.  With zero off-diagonal entries the results are those of box_stride 3 bit for
+ * bit.  A frame whose diagonal entry is not positive and finite, or whose lower off-diagonal
+ * entry is not finite, is NaN; no other frame is.  This holds for every entry below that takes
+ * box_stride, and for aggf_pair_dist_var_pbc / aggf_pair_dist_moments_pbc and aggf_make_whole.
+ *
  * aggf_pair_list_dist_pbc / aggf_pair_list_pull_pbc: the arguments, launch plan and guarantees
- *   of aggf_pair_list_dist / aggf_pair_list_pull, plus the box (NULL or a stride other than 0
- *   or 3: AGGF_ERR_ARG).
+ *   of aggf_pair_list_dist / aggf_pair_list_pull, plus the box (NULL or a stride other than 0,
+ *   3 or 9: AGGF_ERR_ARG).
  * aggf_pair_min (K9e): out[i,j] = min_t |X[t,j] - C[t,i]| (m, n) in `dtype`; square != 0: the
- *   squared distance.  box NULL: open; else the minimum image as above.  The minimum is taken
+ *   squared distance.  box NULL (box_stride 0 or 3): open; else the minimum image or, with
+ *   box_stride 9, the brick image as above (another stride: AGGF_ERR_ARG).  The minimum is taken
  *   over the squared distances of aggf_pair_dist's arithmetic and rooted once, which gives the
  *   bits of the minimum of aggf_pair_list_dist's distances.  A NaN distance makes its pair NaN.
  *   Frames may be split over workgroups, the partial minima going through ws: ws_bytes >= the
@@ -655,6 +670,14 @@ int aggf_gbasis_sum(const void* d, const void* s, const void* centers, const int
  * value for form 2, and for form 0 beyond the LDS bound (short: AGGF_ERR_WORKSPACE); otherwise ws may be
  * NULL.  No atomics; nothing reads another workgroup's writes within a launch.  T or N zero returns AGGF_OK
  * without a launch.
+ *   Triclinic cells: box_stride 9, `box` (T, 9) as in the K9c / K9d forms above.  n_i is then the triple
+ * (ka, kb, kc) of the brick reduction of x_i - x_parent(i) -- each count 0 where its quotient is not finite,
+ * clamped to 2^15, and the next stage reduced with that count --, element c of an atom's counts (and of
+ * images) is the count of lattice vector c (a, b, c in that order), the sums along the root paths are the
+ * same integer sums, and out_i = x_i - kc c - kb b - ka a as nested fmas in that order, component by
+ * component.  With zero off-diagonal entries counts and coordinates are those of box_stride 3 bit for bit.  A
+ * bad frame (above) has counts 0 and NaN coordinates in every component.  The LDS form stages nine numbers
+ * per frame where a box stages six and takes one atom fewer: aggf_make_whole_lds_max_sites() - 1.
  * ------------------------------------------------------------------------- */
 int32_t aggf_make_whole_lds_max_sites(void);
 size_t aggf_make_whole_workspace_bytes(int64_t T, int32_t N, int32_t rounds, int dtype);
@@ -737,7 +760,9 @@ int aggf_pair_dist_moments(const void* X, int64_t T, int32_t N, int dtype, doubl
  * A length that is not a positive finite number makes its frame NaN, and with it every off-diagonal
  * element of var (and mean); the diagonal stays 0.  Plan, workspace (aggf_pair_dist_var_workspace_bytes),
  * summation order and symmetry are those of the open entry points; where every |d| is far below L / 2
- * the results are theirs bit for bit. */
+ * the results are theirs bit for bit.  box_stride 9: `box` is (T, 9), a triclinic cell per frame as in the
+ * K9c / K9d forms, widened to float64, and every displacement is its brick image in float64 (d0: frame 0's
+ * under frame 0's cell); a bad frame is NaN as above. */
 int aggf_pair_dist_var_pbc(const void* X, int64_t T, int32_t N, int dtype, const void* box,
                            int32_t box_stride, double* var, void* ws, size_t ws_bytes, void* stream);
 int aggf_pair_dist_moments_pbc(const void* X, int64_t T, int32_t N, int dtype, const void* box,
