@@ -1118,10 +1118,12 @@ def pair_pool_term(var_r: torch.Tensor, mean_r: torch.Tensor, mean: torch.Tensor
 
 
 def gauss_pair_forces(x: torch.Tensor, offset: float, width: float, want_forces: bool = True,
-                      want_energies: bool = False):
-    """(G (T, n, 3) or None, E (T,) or None) in x's dtype for one squared-distance Gaussian; see aggf_gauss_pair_forces."""
+                      want_energies: bool = False, box: Optional[torch.Tensor] = None):
+    """(G (T, n, 3) or None, E (T,) or None) in x's dtype for one squared-distance Gaussian; see aggf_gauss_pair_forces.
+    ``box`` ((3,), (T, 3) or the (T, 9) rows of a cell, in x's dtype): every r_i - r_j is its image under it."""
     l = lib()
     T, n, _ = x.shape
+    stride = 0 if box is None else _box_arg("gauss_pair_forces", box, x, cell=True)
     G = torch.empty_like(x) if want_forces else None
     E = torch.empty(T, dtype=x.dtype, device=x.device) if want_energies else None
     if x.numel() == 0:
@@ -1129,29 +1131,36 @@ def gauss_pair_forces(x: torch.Tensor, offset: float, width: float, want_forces:
     need = l.aggf_gauss_pair_forces_workspace_bytes(T, n) if want_energies else 0
     ws = workspace(need, x.device, "mapval") if want_energies else None
     with _timed("gauss_forces"):
-        check(l.aggf_gauss_pair_forces(ptr(x), T, n, dtype_code(x.dtype), float(offset), float(width), ptr(G), ptr(E),
-                                       ptr(ws), need, stream_ptr()), "aggf_gauss_pair_forces")
+        check(l.aggf_gauss_pair_forces(ptr(x), T, n, dtype_code(x.dtype), float(offset), float(width), ptr(box), stride,
+                                       ptr(G), ptr(E), ptr(ws), need, stream_ptr()), "aggf_gauss_pair_forces")
     return G, E
 
 
-def gauss_proj(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float) -> torch.Tensor:
-    """(S,) float64: sum over frames and sites of F . G_s for every offset; see aggf_gauss_proj."""
+def gauss_proj(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float,
+               box: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(S,) float64: sum over frames and sites of F . G_s for every offset; see aggf_gauss_proj.  ``box``: as
+    ``gauss_pair_forces``."""
     l = lib()
     T, n, _ = x.shape
+    stride = 0 if box is None else _box_arg("gauss_proj", box, x, cell=True)
     S = offsets.numel()
     out = torch.empty(S, dtype=torch.float64, device=x.device)
     need = l.aggf_gauss_proj_workspace_bytes(T, n, S)
     ws = workspace(need, x.device, "mapval")
     with _timed("gauss_proj"):
         check(l.aggf_gauss_proj(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
-                                float(width), ptr(out), ptr(ws), need, stream_ptr()), "aggf_gauss_proj")
+                                float(width), ptr(box), stride, ptr(out), ptr(ws), need, stream_ptr()),
+              "aggf_gauss_proj")
     return out
 
 
-def gauss_shift(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float):
-    """((S,), (S,)) float64: sum F . G_s and sum |G_s|^2 for every offset, one pass; see aggf_gauss_shift."""
+def gauss_shift(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float,
+                box: Optional[torch.Tensor] = None):
+    """((S,), (S,)) float64: sum F . G_s and sum |G_s|^2 for every offset, one pass; see aggf_gauss_shift.  ``box``:
+    as ``gauss_pair_forces``."""
     l = lib()
     T, n, _ = x.shape
+    stride = 0 if box is None else _box_arg("gauss_shift", box, x, cell=True)
     S = offsets.numel()
     ip = torch.empty(S, dtype=torch.float64, device=x.device)
     gsq = torch.empty(S, dtype=torch.float64, device=x.device)
@@ -1159,7 +1168,8 @@ def gauss_shift(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: 
     ws = workspace(need, x.device, "mapval")
     with _timed("gauss_shift"):
         check(l.aggf_gauss_shift(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
-                                 float(width), ptr(ip), ptr(gsq), ptr(ws), need, stream_ptr()), "aggf_gauss_shift")
+                                 float(width), ptr(box), stride, ptr(ip), ptr(gsq), ptr(ws), need, stream_ptr()),
+              "aggf_gauss_shift")
     return ip, gsq
 
 

@@ -121,11 +121,13 @@ PROTOTYPES = {
     "aggf_concat_sites": (C.c_int, [_vp, _i32, C.c_int, _vp, _i32, C.c_int, _i64, _vp, C.c_int, _vp]),
     "aggf_scale": (C.c_int, [_vp, _i64, C.c_int, _dbl, _vp, _vp]),
     "aggf_gauss_pair_forces_workspace_bytes": (_sz, [_i64, _i32]),
-    "aggf_gauss_pair_forces": (C.c_int, [_vp, _i64, _i32, C.c_int, _dbl, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    "aggf_gauss_pair_forces": (C.c_int, [_vp, _i64, _i32, C.c_int, _dbl, _dbl, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "aggf_gauss_proj_workspace_bytes": (_sz, [_i64, _i32, _i64]),
-    "aggf_gauss_proj": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
+    "aggf_gauss_proj": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _i32, _vp, _vp, _sz,
+                                  _vp]),
     "aggf_gauss_shift_workspace_bytes": (_sz, [_i64, _i32, _i64]),
-    "aggf_gauss_shift": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    "aggf_gauss_shift": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _i32, _vp, _vp, _vp, _sz,
+                                   _vp]),
     "aggf_dot_workspace_bytes": (_sz, []),
     "aggf_dot": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _vp, _vp, _sz, _vp]),
     "aggf_synth_normal": (C.c_int, [_vp, _i64, _i32, C.c_int, _u64, _i64, _dbl, _dbl, _dbl, _vp]),

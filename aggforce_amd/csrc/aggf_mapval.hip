@@ -17,6 +17,13 @@
 // Precision: float64 when either input is float64, float32 with the hardware exp2 when both are float32; every sum
 // over pairs, sites and frames is float64.  Partial sums go to slabs (one per workgroup) and are combined in a fixed
 // order: two runs are bit-identical.  x is formed from the differences r_i - r_j.
+// Periodic forms (template argument PBC of the three gauss kernels; the open forms keep their arithmetic and bits): every
+// displacement d = r_i - r_j is replaced by its image under the frame's cell before x = |d|^2 is formed, so
+// E_t = sum_{i,j} g(|d_ij|^2) (the diagonal is d = 0) and G_i = (8 / w^2) sum_j (x_ij - o) g(x_ij) d_ij.  The image is
+// exactly odd, so the pair form of the projection stands: u = d . (F_i - F_j).  There is ONE periodic form: it holds a
+// CellFrame per frame and takes the brick image (aggf_common.h); the lengths of an orthorhombic box are loaded as a
+// cell without off-diagonal entries, which is min_image bit for bit (fma(-k, 0, d) == d).  A frame whose box or cell
+// is bad (box_lengths, cell_good) has NaN images: its G and E are NaN, and so is every sample of a fused reduction.
 #include "aggf_common.h"
 
 namespace aggf {
@@ -62,6 +69,24 @@ __device__ __forceinline__ C sq_norm3(C d0, C d1, C d2) {
   return d0 * d0 + d1 * d1 + d2 * d2;
 }
 
+// The cell of frame t in the compute type C.  `box` is in X's dtype: (T, 9) row-major cells (bstride 9), or the lengths
+// of an orthorhombic box, (T, 3) (bstride 3) or (3,) (bstride 0), as a cell with zero off-diagonal entries.
+template <typename C, typename TX>
+__device__ __forceinline__ void mv_cell(const TX* __restrict__ box, int32_t bstride, int64_t t, CellFrame<C>& h) {
+  const bool tri = bstride == 9;
+  const TX* m = box + t * bstride;
+  const TX zero = (TX)0, inf = (TX)__builtin_inf();
+  const TX ax = m[0], by = m[tri ? 4 : 1], cz = m[tri ? 8 : 2];
+  const TX bx = tri ? m[3] : zero, cx = tri ? m[6] : zero, cy = tri ? m[7] : zero;
+  // cell_good's rule, which for a box is box_lengths': positive finite lengths (the whole frame is NaN otherwise)
+  const bool ok = ax > zero && ax < inf && by > zero && by < inf && cz > zero && cz < inf && __builtin_fabs(bx) < inf &&
+                  __builtin_fabs(cx) < inf && __builtin_fabs(cy) < inf;
+  const C nan = (C)__builtin_nan("");
+  h.ax = ok ? (C)ax : nan, h.bx = ok ? (C)bx : nan, h.by = ok ? (C)by : nan;
+  h.cx = ok ? (C)cx : nan, h.cy = ok ? (C)cy : nan, h.cz = ok ? (C)cz : nan;
+  h.iax = (C)1 / h.ax, h.iby = (C)1 / h.by, h.icz = (C)1 / h.cz;
+}
+
 // pair index p in [0, n (n - 1) / 2) -> (i, j), i < j, row by row of the strict upper triangle
 __device__ __forceinline__ int64_t pair_row_start(int64_t i, int64_t n) { return i * (n - 1) - i * (i - 1) / 2; }
 __device__ __forceinline__ void pair_of(int64_t p, int64_t n, int64_t* pi, int64_t* pj) {
@@ -77,12 +102,13 @@ __device__ __forceinline__ void pair_of(int64_t p, int64_t n, int64_t* pi, int64
 
 // ---- one offset: G (T, n, 3) and per-(frame, site block) energy partials.  Thread = (frame, site i); a workgroup
 // holds `fpb` frames x `iblk` sites (n <= 256: whole frames, 256 / n of them; else 1 frame x 256 sites) and stages
-// the j sites of its frames in LDS, MV_JT at a time.
-template <typename TX>
+// the j sites of its frames in LDS, MV_JT at a time.  PBC: a thread holds the cell of its own frame.
+template <typename TX, bool PBC>
 __global__ __launch_bounds__(MV_THREADS) void gauss_site_forces_kernel(const TX* __restrict__ X, int64_t T, int32_t n,
                                                                         int32_t fpb, int32_t iblk, int32_t n_iblk,
                                                                         int64_t n_blocks, TX offset, TX k, double scale,
-                                                                        TX* __restrict__ G, double* __restrict__ eslab) {
+                                                                        TX* __restrict__ G, double* __restrict__ eslab,
+                                                                        const TX* __restrict__ box, int32_t bstride) {
   __shared__ TX sx[MV_JT * 3];
   __shared__ double se[MV_THREADS];
   const int tid = threadIdx.x;
@@ -102,6 +128,8 @@ __global__ __launch_bounds__(MV_THREADS) void gauss_site_forces_kernel(const TX*
       r1 = xi[1];
       r2 = xi[2];
     }
+    CellFrame<TX> h = {};
+    if (PBC && active) mv_cell(box, bstride, t, h);
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, e = 0.0;
     for (int64_t j0 = 0; j0 < n; j0 += MV_JT) {
       const int jn = (int)(n - j0 < MV_JT ? n - j0 : MV_JT);
@@ -114,7 +142,8 @@ __global__ __launch_bounds__(MV_THREADS) void gauss_site_forces_kernel(const TX*
       if (active) {
         const TX* base = sx + f * jn * 3;
         for (int j = 0; j < jn; ++j) {
-          const TX d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
+          TX d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
+          if (PBC) brick_image(d0, d1, d2, h);
           const TX tt = sq_norm3(d0, d1, d2) - offset;
           const TX g = Gauss<TX>::g(tt, k);
           const double c = (double)(tt * g);
@@ -155,13 +184,15 @@ __global__ __launch_bounds__(256) void gauss_energy_finish_kernel(const double* 
 }
 
 // ---- S offsets, projection, pair form.  Grid (K splits of the T * n (n - 1) / 2 entries, offset chunks).
-// slabs[k][s] = sum over split k of (x - o_s) g_s(x) u.
-template <typename TX, typename TF>
+// slabs[k][s] = sum over split k of (x - o_s) g_s(x) u.  PBC: d is wrapped once per staged entry, under the cell of the
+// entry's own frame (a stage, and a split, span several frames).
+template <typename TX, typename TF, bool PBC>
 __global__ __launch_bounds__(MV_THREADS) void gauss_proj_kernel(const TX* __restrict__ X, const TF* __restrict__ F,
                                                                  int64_t T, int32_t n,
                                                                  const double* __restrict__ offsets, int64_t S,
                                                                  double width, int64_t per_split,
-                                                                 double* __restrict__ slabs) {
+                                                                 double* __restrict__ slabs,
+                                                                 const TX* __restrict__ box, int32_t bstride) {
   typedef typename Promote<TX, TF>::type C;
   __shared__ C sx[MV_PL], su[MV_PL];
   const int tid = threadIdx.x;
@@ -189,7 +220,12 @@ __global__ __launch_bounds__(MV_THREADS) void gauss_proj_kernel(const TX* __rest
       const TX* xj = X + (t * n + j) * 3;
       const TF* fi = F + (t * n + i) * 3;
       const TF* fj = F + (t * n + j) * 3;
-      const C d0 = (C)xi[0] - (C)xj[0], d1 = (C)xi[1] - (C)xj[1], d2 = (C)xi[2] - (C)xj[2];
+      C d0 = (C)xi[0] - (C)xj[0], d1 = (C)xi[1] - (C)xj[1], d2 = (C)xi[2] - (C)xj[2];
+      if (PBC) {
+        CellFrame<C> h;
+        mv_cell(box, bstride, t, h);
+        brick_image(d0, d1, d2, h);
+      }
       sx[m] = sq_norm3(d0, d1, d2);
       su[m] = d0 * ((C)fi[0] - (C)fj[0]) + d1 * ((C)fi[1] - (C)fj[1]) + d2 * ((C)fi[2] - (C)fj[2]);
     }
@@ -214,12 +250,14 @@ __global__ __launch_bounds__(MV_THREADS) void gauss_proj_kernel(const TX* __rest
 
 // ---- S offsets, residual shift, per-site form.  Grid (K splits of the frames, offset chunks).
 // slabs[k][s][0] = sum F_i . G~_s,i, slabs[k][s][1] = sum |G~_s,i|^2 over split k's frames, G~ = G w^2 / 8.
-template <typename TX, typename TF>
+// PBC: d is wrapped inside the j loop, under the cell of frame f (workgroup-uniform; a `whole` stage holds several).
+template <typename TX, typename TF, bool PBC>
 __global__ __launch_bounds__(MV_THREADS) void gauss_shift_kernel(const TX* __restrict__ X, const TF* __restrict__ F,
                                                                   int64_t T, int32_t n,
                                                                   const double* __restrict__ offsets, int64_t S,
                                                                   double width, int64_t frames_per_split,
-                                                                  double* __restrict__ slabs) {
+                                                                  double* __restrict__ slabs,
+                                                                  const TX* __restrict__ box, int32_t bstride) {
   typedef typename Promote<TX, TF>::type C;
   __shared__ C sx[MV_JT * 3];
   const int tid = threadIdx.x;
@@ -247,6 +285,8 @@ __global__ __launch_bounds__(MV_THREADS) void gauss_shift_kernel(const TX* __res
     }
     for (int f = 0; f < nf; ++f) {
       const int64_t t = t0 + f;
+      CellFrame<C> h = {};
+      if (PBC) mv_cell(box, bstride, t, h);
       for (int64_t i = 0; i < n; ++i) {
         const TX* xi = X + (t * n + i) * 3;
         const TF* fi = F + (t * n + i) * 3;
@@ -273,7 +313,8 @@ __global__ __launch_bounds__(MV_THREADS) void gauss_shift_kernel(const TX* __res
             __syncthreads();
           }
           for (int j = 0; j < jn; ++j) {
-            const C d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
+            C d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
+            if (PBC) brick_image(d0, d1, d2, h);
             const C x = sq_norm3(d0, d1, d2);
             const double e0 = (double)d0, e1 = (double)d1, e2 = (double)d2;
 #pragma unroll
@@ -393,6 +434,13 @@ static SplitPlan split_plan(int64_t units, int64_t min_units, int64_t S, int W) 
   return p;
 }
 
+// box NULL: the open kernels; else (T, 9) cells, (T, 3) or (3,) lengths by its stride
+static int mv_box(const char* who, const void* box, int32_t box_stride) {
+  if (box && box_stride != 0 && box_stride != 3 && box_stride != 9)
+    return fail(AGGF_ERR_ARG, "%s: box_stride %d is none of 0, 3 and 9", who, box_stride);
+  return AGGF_OK;
+}
+
 static bool mv_samples_ok(int64_t S) { return S > 0 && ceil_div(S, MV_SCHUNK) <= 65535; }
 
 static size_t proj_ws(int64_t T, int32_t n, int64_t S) {
@@ -414,13 +462,29 @@ extern "C" size_t aggf_gauss_pair_forces_workspace_bytes(int64_t T, int32_t n) {
   return (size_t)(T * p.n_iblk) * sizeof(double) + 256;
 }
 
+template <typename TX>
+static void launch_site(dim3 grid, hipStream_t stream, const void* X, int64_t T, int32_t n, const SitePlan& p,
+                        double offset, double width, void* G, double* eslab, const void* box, int32_t bstride) {
+  const TX k = Gauss<TX>::coef(width);
+  const double scale = 8.0 / (width * width);
+  if (box)
+    AGGF_LAUNCH((gauss_site_forces_kernel<TX, true>), grid, dim3(MV_THREADS), 0, stream, (const TX*)X, T, n, p.fpb,
+                p.iblk, p.n_iblk, p.n_blocks, (TX)offset, k, scale, (TX*)G, eslab, (const TX*)box, bstride);
+  else
+    AGGF_LAUNCH((gauss_site_forces_kernel<TX, false>), grid, dim3(MV_THREADS), 0, stream, (const TX*)X, T, n, p.fpb,
+                p.iblk, p.n_iblk, p.n_blocks, (TX)offset, k, scale, (TX*)G, eslab, (const TX*)nullptr, 0);
+}
+
 extern "C" int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
-                                      void* G, void* E, void* ws, size_t ws_bytes, void* stream_v) {
+                                      const void* box, int32_t box_stride, void* G, void* E, void* ws, size_t ws_bytes,
+                                      void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   if (!X || (!G && !E)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: NULL pointer");
   if (!mv_dtype_ok(dtype)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: bad dtype");
   if (!mv_shape_ok(T, n)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: bad shape (T=%lld, n=%d)", (long long)T, n);
   if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: width must be positive");
+  const int rcb = mv_box("aggf_gauss_pair_forces", box, box_stride);
+  if (rcb != AGGF_OK) return rcb;
   const SitePlan p = site_plan(T, n);
   double* eslab = nullptr;
   if (E) {
@@ -430,17 +494,14 @@ extern "C" int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int d
     eslab = (double*)ws;
   }
   const dim3 grid((unsigned)(p.n_blocks < MV_MAX_GRID ? p.n_blocks : MV_MAX_GRID));
-  const double scale = 8.0 / (width * width);
   const int64_t fg = ceil_div(T, 256) < 4096 ? ceil_div(T, 256) : 4096;
   if (dtype == AGGF_F64) {
-    AGGF_LAUNCH(gauss_site_forces_kernel<double>, grid, dim3(MV_THREADS), 0, stream, (const double*)X, T, n, p.fpb,
-                p.iblk, p.n_iblk, p.n_blocks, offset, Gauss<double>::coef(width), scale, (double*)G, eslab);
+    launch_site<double>(grid, stream, X, T, n, p, offset, width, G, eslab, box, box_stride);
     AGGF_LAUNCH_OK();
     if (E) AGGF_LAUNCH(gauss_energy_finish_kernel<double>, dim3((unsigned)fg), dim3(256), 0, stream, eslab, T, p.n_iblk,
                        (double*)E);
   } else {
-    AGGF_LAUNCH(gauss_site_forces_kernel<float>, grid, dim3(MV_THREADS), 0, stream, (const float*)X, T, n, p.fpb,
-                p.iblk, p.n_iblk, p.n_blocks, (float)offset, Gauss<float>::coef(width), scale, (float*)G, eslab);
+    launch_site<float>(grid, stream, X, T, n, p, offset, width, G, eslab, box, box_stride);
     AGGF_LAUNCH_OK();
     if (E) AGGF_LAUNCH(gauss_energy_finish_kernel<float>, dim3((unsigned)fg), dim3(256), 0, stream, eslab, T, p.n_iblk,
                        (float*)E);
@@ -459,56 +520,56 @@ extern "C" size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t
   return shift_ws(T, S);
 }
 
-template <typename TX>
-static void launch_proj_x(const TX* X, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets,
-                          int64_t S, double width, const SplitPlan& p, double* slabs, hipStream_t stream) {
-  const dim3 grid((unsigned)p.K, (unsigned)p.n_sch);
-  if (f_dtype == AGGF_F64)
-    AGGF_LAUNCH((gauss_proj_kernel<TX, double>), grid, dim3(MV_THREADS), 0, stream, X, (const double*)F, T, n, offsets,
-                S, width, p.per_split, slabs);
-  else
-    AGGF_LAUNCH((gauss_proj_kernel<TX, float>), grid, dim3(MV_THREADS), 0, stream, X, (const float*)F, T, n, offsets,
-                S, width, p.per_split, slabs);
-}
-
-template <typename TX>
-static void launch_shift_x(const TX* X, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets,
-                           int64_t S, double width, const SplitPlan& p, double* slabs, hipStream_t stream) {
-  const dim3 grid((unsigned)p.K, (unsigned)p.n_sch);
-  if (f_dtype == AGGF_F64)
-    AGGF_LAUNCH((gauss_shift_kernel<TX, double>), grid, dim3(MV_THREADS), 0, stream, X, (const double*)F, T, n,
-                offsets, S, width, p.per_split, slabs);
-  else
-    AGGF_LAUNCH((gauss_shift_kernel<TX, float>), grid, dim3(MV_THREADS), 0, stream, X, (const float*)F, T, n, offsets,
-                S, width, p.per_split, slabs);
-}
+// (box NULL: the open instantiation)
+#define AGGF_MV_LAUNCH(KERNEL, TF, PBC, BOX, STRIDE)                                                               \
+  AGGF_LAUNCH((KERNEL<TX, TF, PBC>), grid, dim3(MV_THREADS), 0, stream, X, (const TF*)F, T, n, offsets, S, width,  \
+              p.per_split, slabs, BOX, STRIDE)
+#define AGGF_MV_LAUNCH_X(NAME, KERNEL)                                                                             \
+  template <typename TX>                                                                                           \
+  static void NAME(const TX* X, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets, int64_t S, \
+                   double width, const SplitPlan& p, double* slabs, const void* box, int32_t bstride,              \
+                   hipStream_t stream) {                                                                           \
+    const dim3 grid((unsigned)p.K, (unsigned)p.n_sch);                                                             \
+    if (box && f_dtype == AGGF_F64)                                                                                \
+      AGGF_MV_LAUNCH(KERNEL, double, true, (const TX*)box, bstride);                                               \
+    else if (box)                                                                                                  \
+      AGGF_MV_LAUNCH(KERNEL, float, true, (const TX*)box, bstride);                                                \
+    else if (f_dtype == AGGF_F64)                                                                                  \
+      AGGF_MV_LAUNCH(KERNEL, double, false, (const TX*)nullptr, 0);                                                \
+    else                                                                                                           \
+      AGGF_MV_LAUNCH(KERNEL, float, false, (const TX*)nullptr, 0);                                                 \
+  }
+AGGF_MV_LAUNCH_X(launch_proj_x, gauss_proj_kernel)
+AGGF_MV_LAUNCH_X(launch_shift_x, gauss_shift_kernel)
+#undef AGGF_MV_LAUNCH_X
+#undef AGGF_MV_LAUNCH
 
 static int mv_check(const char* who, const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
-                    const double* offsets, int64_t S, double width, const void* out0, const void* out1, const void* ws,
-                    size_t ws_bytes, size_t need) {
+                    const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                    const void* out0, const void* out1, const void* ws, size_t ws_bytes, size_t need) {
   if (!X || !F || !offsets || !out0 || !out1 || !ws) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
   if (!mv_dtype_ok(x_dtype) || !mv_dtype_ok(f_dtype)) return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
   if (!mv_shape_ok(T, n)) return fail(AGGF_ERR_ARG, "%s: bad shape (T=%lld, n=%d)", who, (long long)T, n);
   if (!mv_samples_ok(S)) return fail(AGGF_ERR_ARG, "%s: bad sample count %lld", who, (long long)S);
   if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "%s: width must be positive", who);
   if (ws_bytes < need - 256) return fail(AGGF_ERR_WORKSPACE, "%s: workspace too small", who);
-  return AGGF_OK;
+  return mv_box(who, box, box_stride);
 }
 
 extern "C" int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
-                               const double* offsets, int64_t S, double width, double* out, void* ws, size_t ws_bytes,
-                               void* stream_v) {
+                               const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                               double* out, void* ws, size_t ws_bytes, void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   const size_t need = mv_shape_ok(T, n) && mv_samples_ok(S) ? proj_ws(T, n, S) : 256;
-  const int rc = mv_check("aggf_gauss_proj", X, x_dtype, F, f_dtype, T, n, offsets, S, width, out, out, ws, ws_bytes,
-                          need);
+  const int rc = mv_check("aggf_gauss_proj", X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, out, out,
+                          ws, ws_bytes, need);
   if (rc != AGGF_OK) return rc;
   const SplitPlan p = split_plan(T * ((int64_t)n * (n - 1) / 2), MV_PL, S, 1);
   double* slabs = (double*)ws;
   if (x_dtype == AGGF_F64)
-    launch_proj_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+    launch_proj_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
   else
-    launch_proj_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+    launch_proj_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
   AGGF_LAUNCH_OK();
   const int64_t g = ceil_div(S, 256) < 1024 ? ceil_div(S, 256) : 1024;
   AGGF_LAUNCH(mapval_slab_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, slabs, p.K, S, 1,
@@ -518,19 +579,19 @@ extern "C" int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_
 }
 
 extern "C" int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
-                                const double* offsets, int64_t S, double width, double* ip, double* gsq, void* ws,
-                                size_t ws_bytes, void* stream_v) {
+                                const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                                double* ip, double* gsq, void* ws, size_t ws_bytes, void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   const size_t need = mv_shape_ok(T, n) && mv_samples_ok(S) ? shift_ws(T, S) : 256;
-  const int rc = mv_check("aggf_gauss_shift", X, x_dtype, F, f_dtype, T, n, offsets, S, width, ip, gsq, ws, ws_bytes,
-                          need);
+  const int rc = mv_check("aggf_gauss_shift", X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, ip, gsq,
+                          ws, ws_bytes, need);
   if (rc != AGGF_OK) return rc;
   const SplitPlan p = split_plan(T, 1, S, 2);
   double* slabs = (double*)ws;
   if (x_dtype == AGGF_F64)
-    launch_shift_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+    launch_shift_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
   else
-    launch_shift_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, stream);
+    launch_shift_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
   AGGF_LAUNCH_OK();
   const double sc = 8.0 / (width * width);
   const int64_t g = ceil_div(S, 256) < 1024 ? ceil_div(S, 256) : 1024;

@@ -195,22 +195,28 @@ int main() {
   REFUSED(aggf_pair_dist_moments_pbc(p, 10, 5, 1, p, 3, nullptr, d, ws, WS, nullptr));         // no mean
   REFUSED(aggf_pair_dist_moments_pbc(p, 10, 0, 0, p, 0, d, d + 4096, ws, WS, nullptr));
   // K7: NULL pointers, bad shapes / dtypes / sample counts, widths that are not positive, short workspaces
-  REFUSED(aggf_gauss_pair_forces(nullptr, 10, 5, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, nullptr, ws, WS, nullptr));  // neither G nor E
-  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, p, nullptr, WS, nullptr));  // E without workspace
-  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, p, ws, 8, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, 0, 5, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, 10, 0, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, (int64_t)1 << 40, 20000, 1, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 2, 1.0, 0.5, p, nullptr, ws, WS, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.0, p, nullptr, ws, WS, nullptr));
-  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, -1.0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(nullptr, 10, 5, 1, 1.0, 0.5, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, 0, nullptr, nullptr, ws, WS, nullptr));  // no G, no E
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, 0, nullptr, p, nullptr, WS, nullptr));  // E, no workspace
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, nullptr, 0, nullptr, p, ws, 8, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 0, 5, 1, 1.0, 0.5, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 0, 1, 1.0, 0.5, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, (int64_t)1 << 40, 20000, 1, 1.0, 0.5, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 2, 1.0, 0.5, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.0, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, -1.0, nullptr, 0, p, nullptr, ws, WS, nullptr));
+  for (int32_t stride : {-3, 1, 2, 6, 12})  // a box whose stride is none of 0, 3 and 9
+    REFUSED(aggf_gauss_pair_forces(p, 10, 5, 1, 1.0, 0.5, p, stride, p, nullptr, ws, WS, nullptr));
   for (int shift = 0; shift < 2; ++shift) {
     auto call = [&](const void* X, int xd, const void* F, int fd, int64_t T, int32_t n, const double* o, int64_t S,
                     double w, double* out, size_t wsb) {
-      return shift ? aggf_gauss_shift(X, xd, F, fd, T, n, o, S, w, out, out ? d + 4096 : nullptr, ws, wsb, nullptr)
-                   : aggf_gauss_proj(X, xd, F, fd, T, n, o, S, w, out, ws, wsb, nullptr);
+      return shift ? aggf_gauss_shift(X, xd, F, fd, T, n, o, S, w, nullptr, 0, out, out ? d + 4096 : nullptr, ws, wsb,
+                                      nullptr)
+                   : aggf_gauss_proj(X, xd, F, fd, T, n, o, S, w, nullptr, 0, out, ws, wsb, nullptr);
     };
+    for (int32_t stride : {-3, 1, 2, 6, 12})
+      REFUSED(shift ? aggf_gauss_shift(p, 1, p, 1, 10, 5, d, 4, 0.5, p, stride, d, d + 4096, ws, WS, nullptr)
+                    : aggf_gauss_proj(p, 1, p, 1, 10, 5, d, 4, 0.5, p, stride, d, ws, WS, nullptr));
     REFUSED(call(nullptr, 1, p, 1, 10, 5, d, 4, 0.5, d, WS));
     REFUSED(call(p, 1, nullptr, 1, 10, 5, d, 4, 0.5, d, WS));
     REFUSED(call(p, 1, p, 1, 10, 5, nullptr, 4, 0.5, d, WS));
@@ -307,11 +313,18 @@ int main() {
         for (int xd = 0; xd < 2; ++xd)
           for (int fd = 0; fd < 2; ++fd) {
             if (fd == 0 && S == 1) {
-              if (wf <= WS) RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, p, (char*)p + 4096, ws, wf, nullptr));
-              RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, p, nullptr, nullptr, 0, nullptr));
+              if (wf <= WS)
+                RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, nullptr, 0, p, (char*)p + 4096, ws, wf, nullptr));
+              RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, nullptr, 0, p, nullptr, nullptr, 0, nullptr));
+              for (int32_t stride : {0, 3, 9})  // under a box or a cell: the same plan and workspace
+                RUNS(aggf_gauss_pair_forces(p, T, n, xd, 37.0, 0.25, p, stride, p, nullptr, nullptr, 0, nullptr));
             }
-            if (wpj <= WS) RUNS(aggf_gauss_proj(p, xd, p, fd, T, n, d, S, 0.25, d + 4096, ws, wpj, nullptr));
-            if (wsh <= WS) RUNS(aggf_gauss_shift(p, xd, p, fd, T, n, d, S, 0.25, d + 4096, d + 8192, ws, wsh, nullptr));
+            for (int32_t stride : {-1, 0, 3, 9}) {  // (-1: open)
+              const void* box = stride < 0 ? nullptr : p;
+              if (wpj <= WS) RUNS(aggf_gauss_proj(p, xd, p, fd, T, n, d, S, 0.25, box, stride, d + 4096, ws, wpj, nullptr));
+              if (wsh <= WS)
+                RUNS(aggf_gauss_shift(p, xd, p, fd, T, n, d, S, 0.25, box, stride, d + 4096, d + 8192, ws, wsh, nullptr));
+            }
             RUNS(aggf_dot(p, xd, (char*)p + 4096, fd, T * n * 3, d, ws, aggf_dot_workspace_bytes(), nullptr));
           }
       }

@@ -9,6 +9,18 @@ state afterwards, as one ``randg.random()`` per sample) and ONE kernel pass over
 (``aggf_gauss_proj`` / ``aggf_gauss_shift``, K7).  Any other ``method`` is called once per sample, as in the
 reference, and reduced on the device (``aggf_dot``).
 
+Periodic boundaries (not in the reference): ``random_force_proj(..., box=B)`` and ``random_residual_shift(..., box=B)``
+with the default method measure every pair displacement as its image under ``B`` -- the lengths of an orthorhombic box,
+``(3,)`` or ``(n_frames, 3)``, or a ``pbc.Cell`` -- on the periodic forms of the same kernels, still in one pass and
+with the offsets and the generator state of the open call.  The field of an open distance on a wrapped trajectory jumps
+whenever a site crosses a face of the cell: it is not a function of the periodic configuration, and a projection on it
+says nothing about the map.  The single-field forms that take a box are ``pbc.sq_gaussian_energies``,
+``pbc.sq_gaussian_forces`` and ``pbc.rsqpg_forces`` (the names of this module keep the reference's signatures).
+``outer`` must not exceed half the smallest box length (``Cell.safe_radius`` for a cell): beyond it the image switches
+where the field is not small and the field is discontinuous.  That is checked for a box on the host (``ValueError``,
+before any device work) and not for a box on a GPU (no synchronisation).  The Gaussian's tail past ``outer`` is the
+caller's concern: choose ``width`` so that it has decayed at the switching distance.
+
 Deviations from the reference: coordinates and forces must both have the shape ``(n_frames, n_sites, 3)`` and
 ``width`` must be positive (``ValueError``; the reference returns NaN / inf there); the residual shift is evaluated
 as ``(sum |G|^2 - 2 sum F . G) / F.size``, which equals the reference's ``force_smoothness(F - G) -
@@ -21,8 +33,10 @@ import numpy as np
 import numpy.random as r
 
 from . import _kernels as K
+from ._cell import is_cell_rows
+from .jaxutil import _as_box
 
-_FAST_KWARGS = frozenset({"inner", "outer", "width", "sq_args"})
+_FAST_KWARGS = frozenset({"inner", "outer", "width", "sq_args", "box"})
 
 
 def _shape_of(x) -> tuple:
@@ -99,22 +113,54 @@ def _draw_offsets(randg: r.Generator, n_samples: int, inner, outer, width, sq_ar
     return randg.random(n_samples) * interval_width + inner, width
 
 
+def _host_box(box, n_frames: int, outer=None, sq_args: bool = True):
+    """``box`` normalised (``jaxutil._as_box``: (3,), (n_frames, 3) or the (n_frames, 9) rows of a ``Cell``), or None.
+    On the host, ``outer`` (if given) as a distance (its square root if it was given squared) must not exceed half the
+    smallest length, ``Cell.safe_radius`` for a cell (``ValueError``); a box on a GPU is not read."""
+    if box is None:
+        return None
+    box = _as_box(box, n_frames)
+    if outer is not None and not box.is_cuda and box.numel():
+        lengths = box[:, [0, 4, 8]] if is_cell_rows(box) else box
+        half = float(lengths.min()) / 2
+        reach = float(outer) if sq_args else float(outer) ** 0.5
+        if reach > half:
+            raise ValueError(f"outer reaches {reach:g}, beyond half the smallest box length ({half:g}): the field is "
+                             "discontinuous where the image switches")
+    return box
+
+
+def _device_box(box, X):
+    return None if box is None else box.to(device=X.device, dtype=X.dtype).contiguous()
+
+
 def _fast_path(method, kwargs) -> bool:
-    return method is rsqpg_forces and set(kwargs) <= _FAST_KWARGS
+    if not set(kwargs) <= _FAST_KWARGS:
+        return False
+    if method is rsqpg_forces:
+        return True
+    from . import pbc
+
+    return method is pbc.rsqpg_forces
 
 
 def _fused(coords, forces, n_samples: int, randg, kwargs, shift: bool) -> List[float]:
     import torch
 
+    kwargs = dict(kwargs)
+    box = kwargs.pop("box", None)
+    if box is not None:
+        box = _host_box(box, _shape_of(coords)[0], kwargs.get("outer"), kwargs.get("sq_args", True))
     offsets, width = _draw_offsets(randg, n_samples, **kwargs)
     X = K.as_device(coords)
     F = K.as_device(forces)
     o = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float64)).to(X.device)
+    under = {} if box is None else {"box": _device_box(box, X)}
     if shift:
-        ip, gsq = (v.cpu().numpy() for v in K.gauss_shift(X, F, o, width))
+        ip, gsq = (v.cpu().numpy() for v in K.gauss_shift(X, F, o, width, **under))
         vals = (gsq - 2.0 * ip) / float(F.numel())
     else:
-        vals = K.gauss_proj(X, F, o, width).cpu().numpy() / float(X.shape[0])
+        vals = K.gauss_proj(X, F, o, width, **under).cpu().numpy() / float(X.shape[0])
     return [float(v) for v in vals]
 
 
@@ -129,7 +175,9 @@ def random_residual_shift(
 ) -> Union[float, List[float]]:
     """Force-residual shift of ``n_samples`` random force fields G_s against the flat one (reference
     jaxmapval.py:159-237): ``force_smoothness(forces - G_s) - force_smoothness(forces)`` per sample, or their mean
-    if ``average``.  ``method(coords, randg=randg, **kwargs)`` makes G_s; the default takes the fused path."""
+    if ``average``.  ``method(coords, randg=randg, **kwargs)`` makes G_s; the default takes the fused path, also with
+    ``box=`` among the keywords (pair displacements as their images under a periodic box or ``pbc.Cell``: the module's
+    text).  Any other method is handed ``box`` like every other keyword."""
     _check_pair(coords, forces)
     if randg is None:
         randg = r.default_rng()
@@ -159,7 +207,9 @@ def random_force_proj(
 ) -> Union[float, Iterable[float]]:
     """MSCG projections of ``forces`` on ``n_samples`` random basis force fields (reference jaxmapval.py:266-319):
     ``mscg_ip(forces, method(coords, randg=randg, **kwargs))`` per sample, or their mean if ``average``.  The
-    default method takes the fused path."""
+    default method takes the fused path, also with ``box=`` among the keywords (pair displacements as their images
+    under a periodic box or ``pbc.Cell``: the module's text).  Any other method is handed ``box`` like every other
+    keyword."""
     _check_pair(coords, forces)
     if randg is None:
         randg = r.default_rng()

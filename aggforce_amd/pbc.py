@@ -40,6 +40,10 @@ forms of the same kernels.  The image of a displacement is its brick reduction (
 
 and the image counts (T, N, 3) are those of a, b, c in that order.  Bonds must be shorter than ``safe_radius``.
 
+Map validation (``jaxmapval``) under a box: ``random_force_proj(..., box=B)`` and ``random_residual_shift(..., box=B)``
+take the fused periodic path; the single-field functions that take a box are here, ``sq_gaussian_energies``,
+``sq_gaussian_forces`` and ``rsqpg_forces`` (``jaxmapval`` keeps the reference's signatures, which have no box).
+
 Out of scope: unwrapping across time (jumps between frames), minimum-image group means, ``aggforce_amd.stream`` for
 host trajectories (it takes no box); under a ``Cell`` also ``gb_feat`` (refused) and ``comm=`` (refused).
 """
@@ -49,6 +53,7 @@ import numpy as np
 import torch
 
 from . import _kernels as K
+from . import mapval as _mv
 from ._cell import Cell, cell_good, is_cell_rows  # noqa: F401  (Cell: part of this module's surface)
 from .jaxutil import PairList, _as_box
 
@@ -376,3 +381,48 @@ class _HostWhole(torch.autograd.Function):
     @staticmethod
     def backward(ctx, H):
         return H, None
+
+
+# ------------------------------------------------------------------ map validation under a box (mapval.py, K7)
+def _mapval_inputs(positions, width, box, outer=None, sq_args: bool = True):
+    """(coordinates on the device, box on the device or None), every argument checked before any device work."""
+    n_frames = _mv._check_trajectory(positions, "positions")[0]
+    _mv._check_width(width)
+    box = _mv._host_box(box, n_frames, outer, sq_args)
+    X = K.as_device(positions)
+    return X, _mv._device_box(box, X)
+
+
+def sq_gaussian_energies(positions, offset: float, width: float, box):
+    """``jaxmapval.sq_gaussian_energies`` under a periodic box: ``E_t = sum_{i,j} exp(-((|d_ij|^2 - offset) / width)^2)``
+    with ``d_ij`` the image of ``r_i - r_j`` under ``box`` -- the lengths of an orthorhombic box, (3,) or
+    (n_frames, 3) (minimum image), or a ``Cell`` (brick image) -- diagonal included (``d = 0``).  Shape (n_frames,),
+    in the container and dtype of ``positions``.  A box on a GPU is not checked: a frame whose box is bad is NaN."""
+    X, b = _mapval_inputs(positions, width, box)
+    _, E = K.gauss_pair_forces(X, offset, width, want_forces=False, want_energies=True, box=b)
+    return K.like_input(E, positions)
+
+
+def sq_gaussian_forces(positions, offset: float, width: float, box):
+    """``jaxmapval.sq_gaussian_forces`` under a periodic box: ``G_i = (8 / width^2) sum_j (x_ij - offset) g(x_ij) d_ij``,
+    ``x_ij = |d_ij|^2``, ``d_ij`` the image of ``r_i - r_j`` under ``box`` (as ``sq_gaussian_energies``) -- the forces
+    of that energy wherever no pair sits where its image switches."""
+    X, b = _mapval_inputs(positions, width, box)
+    G, _ = K.gauss_pair_forces(X, offset, width, box=b)
+    return K.like_input(G, positions)
+
+
+def rsqpg_forces(positions, inner: float, outer: float, width: float, randg=None, sq_args: bool = True, box=None):
+    """``jaxmapval.rsqpg_forces`` with ``box=``: the forces of one random squared-distance Gaussian field of image
+    distances (the same draw from ``randg``).  As ``method`` of ``random_force_proj`` / ``random_residual_shift`` it
+    takes their fused path.  ``outer`` (a distance if ``sq_args``, else a squared one) must not exceed half the
+    smallest box length, ``Cell.safe_radius`` for a cell: ``ValueError`` for a box on the host, not checked for a box
+    on a GPU.  The Gaussian's tail past ``outer`` is the caller's concern."""
+    _mv._check_trajectory(positions, "positions")
+    lo, interval_width, w = _mv._sq_params(inner, outer, width, sq_args)
+    X, b = _mapval_inputs(positions, w, box, outer, sq_args)
+    if randg is None:
+        randg = np.random.default_rng()
+    offset = randg.random() * interval_width + lo
+    G, _ = K.gauss_pair_forces(X, offset, w, box=b)
+    return K.like_input(G, positions)

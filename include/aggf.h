@@ -841,17 +841,26 @@ int aggf_scale(const void* x, int64_t count, int dtype, double alpha, void* out,
  *   aggf_gauss_shift        ip[s] = sum_t sum_i F[t,i] . G_s[t,i], gsq[s] = sum_t sum_i |G_s[t,i]|^2 in one pass
  *                           (the residual shift of sample s is (gsq[s] - 2 ip[s]) / (3 n T));
  *   aggf_dot                out[0] = sum a[k] b[k] over `count` elements (mscg_ip and the generic sample loop).
+ * Periodic boundaries: `box` NULL is the open form above (box_stride is not read).  Otherwise every displacement
+ * r_i - r_j is replaced by its image d before x = |d|^2 is formed, and G_i = (8 / w^2) sum_j (x_ij - o) g(x_ij) d_ij;
+ * the diagonal is d = 0.  `box` is in the dtype of X and box_stride is 0, 3 or 9 as for aggf_pair_list_dist_pbc:
+ * the lengths of an orthorhombic box, (3,) (stride 0) or (T, 3) (stride 3), or a row-major 3 x 3 triclinic cell per
+ * frame, (T, 9) (stride 9: brick reduction, the true minimum image up to min(ax, by, cz) / 2).  A frame whose box or
+ * cell is bad (a length or diagonal entry that is not positive and finite, an off-diagonal entry that is not finite)
+ * has NaN G and E, and makes every out[s], ip[s] and gsq[s] NaN.  Plans and workspaces do not depend on the box.
  * ------------------------------------------------------------------------- */
 size_t aggf_gauss_pair_forces_workspace_bytes(int64_t T, int32_t n);
-int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width, void* G,
-                           void* E, void* ws, size_t ws_bytes, void* stream);
+int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
+                           const void* box, int32_t box_stride, void* G, void* E, void* ws, size_t ws_bytes,
+                           void* stream);
 size_t aggf_gauss_proj_workspace_bytes(int64_t T, int32_t n, int64_t S);
 int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets,
-                    int64_t S, double width, double* out, void* ws, size_t ws_bytes, void* stream);
+                    int64_t S, double width, const void* box, int32_t box_stride, double* out, void* ws,
+                    size_t ws_bytes, void* stream);
 size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t S);
 int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
-                     const double* offsets, int64_t S, double width, double* ip, double* gsq, void* ws,
-                     size_t ws_bytes, void* stream);
+                     const double* offsets, int64_t S, double width, const void* box, int32_t box_stride, double* ip,
+                     double* gsq, void* ws, size_t ws_bytes, void* stream);
 size_t aggf_dot_workspace_bytes(void);
 int aggf_dot(const void* a, int a_dtype, const void* b, int b_dtype, int64_t count, double* out, void* ws,
              size_t ws_bytes, void* stream);
