@@ -305,13 +305,14 @@ def _tables(plist, like: torch.Tensor) -> "K.PairTables":
     return plist.on(like.device) if hasattr(plist, "on") else plist
 
 
-def _box_kw(box, ct: torch.dtype) -> dict:
-    """The ``box`` keyword of a kernel call in the call's dtype; with no box, no keyword (the open call as it was)."""
+def _box_kw(box, ct: torch.dtype, near: bool = False) -> dict:
+    """The ``box`` keyword of a kernel call in the call's dtype; with no box, no keyword (the open call as it was).
+    ``near``: the nearest-image form of a cell's rows (``pbc.Cell(..., images="nearest")``)."""
     if box is None:
         return {}
     if box.requires_grad:
         raise ValueError("box is a constant: gradients with respect to box lengths are not built")
-    return {"box": _widened(box, ct)}
+    return {"box": _widened(box, ct), "near": True} if near else {"box": _widened(box, ct)}
 
 
 class PairListDist(torch.autograd.Function):
@@ -322,27 +323,29 @@ class PairListDist(torch.autograd.Function):
     minimum image under that box (the box forms of K9c / K9d).  The wrap is locally constant, so a derivative differs
     from the open one only in the displacement it multiplies: the box goes to every call that forms a displacement of
     coordinates, and the pulls whose "sites" are tangents (``PairListPull`` / ``PairListDot`` backward) stay open --
-    differences of tangents are not displacements and are never wrapped."""
+    differences of tangents are not displacements and are never wrapped.  ``near`` (with the (T, 9) rows of a cell): the
+    nearest image instead of the brick image, in the forward and -- the backward kernels recompute the displacement --
+    in every derivative, which therefore multiply the image the forward chose."""
 
     @staticmethod
-    def forward(ctx, X, C, plist, square=False, box=None):
+    def forward(ctx, X, C, plist, square=False, box=None, near=False):
         ct = _pair_dtype(X, C)
         D = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_SQDIST if square else K.PAIR_DIST,
-                             **_box_kw(box, ct))
-        ctx.square, ctx.plist, ctx.box = bool(square), plist, box
+                             **_box_kw(box, ct, near))
+        ctx.square, ctx.plist, ctx.box, ctx.near = bool(square), plist, box, bool(near)
         ctx.save_for_backward(X, C, D)
         return D
 
     @staticmethod
     def backward(ctx, H):
         X, C, D = ctx.saved_tensors
-        plist, box = ctx.plist, ctx.box
+        plist, box, near = ctx.plist, ctx.box, ctx.near
         want_x, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (want_x or want_c):
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         if ctx.square and box is not None:  # (2 u, not the image of 2 X - 2 C)
             dX, dC = PairListPull.apply(2 * H, X, C, plist, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c),
-                                        box)
+                                        box, near)
         elif ctx.square:
             dX, dC = PairListPull.apply(H, 2 * X, 2 * C, plist, want_x, want_c,
                                         _pull_dtype(D.dtype, X, C, want_x, want_c))
@@ -350,13 +353,13 @@ class PairListDist(torch.autograd.Function):
             pos = D > 0
             W = torch.where(pos, H / torch.where(pos, D, torch.ones_like(D)), torch.zeros_like(D))
             dX, dC = PairListPull.apply(W, X, C, plist, want_x, want_c, _pull_dtype(D.dtype, X, C, want_x, want_c),
-                                        box)
+                                        box, near)
         else:
             ct = _pair_dtype(H, D)
             dX, dC = K.pair_list_pull(_widened(H, ct), _widened(X, ct), _widened(C, ct), _tables(plist, X),
                                       dv=_widened(D, ct), want_a=want_x, want_b=want_c,
-                                      out_dtype=_pull_dtype(ct, X, C, want_x, want_c), **_box_kw(box, ct))
-        return _as(dX, X.dtype), _as(dC, C.dtype), None, None, None
+                                      out_dtype=_pull_dtype(ct, X, C, want_x, want_c), **_box_kw(box, ct, near))
+        return _as(dX, X.dtype), _as(dC, C.dtype), None, None, None, None
 
 
 class PairListPull(torch.autograd.Function):
@@ -365,29 +368,29 @@ class PairListPull(torch.autograd.Function):
     None.  ``box``: u is the minimum image of X[t,j_p] - C[t,i_p] (see ``PairListDist``)."""
 
     @staticmethod
-    def forward(ctx, W, X, C, plist, want_a=True, want_b=True, out_dtype=None, box=None):
+    def forward(ctx, W, X, C, plist, want_a=True, want_b=True, out_dtype=None, box=None, near=False):
         ct = _pair_dtype(W, X, C) if out_dtype is None else torch.promote_types(_pair_dtype(W, X, C), out_dtype)
         A, B = K.pair_list_pull(_widened(W, ct), _widened(X, ct), _widened(C, ct), _tables(plist, X), want_a=want_a,
-                                want_b=want_b, out_dtype=out_dtype or ct, **_box_kw(box, ct))
-        ctx.plist, ctx.box = plist, box
+                                want_b=want_b, out_dtype=out_dtype or ct, **_box_kw(box, ct, near))
+        ctx.plist, ctx.box, ctx.near = plist, box, bool(near)
         ctx.save_for_backward(W, X, C)
         return A, B
 
     @staticmethod
     def backward(ctx, GA, GB):
         W, X, C = ctx.saved_tensors
-        plist, box = ctx.plist, ctx.box
+        plist, box, near = ctx.plist, ctx.box, ctx.near
         dW = dX = dC = None
         if GA is None and GB is None:
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         ct = _pair_dtype(W, X, C, *(g for g in (GA, GB) if g is not None))
         GA, GB = _zeros_if_none(GA, X, ct), _zeros_if_none(GB, C, ct)
         if ctx.needs_input_grad[0]:
-            dW = _as(PairListDot.apply(GA, GB, X, C, plist, box), W.dtype)
+            dW = _as(PairListDot.apply(GA, GB, X, C, plist, box, near), W.dtype)
         want_x, want_c = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         if want_x or want_c:  # (sums of W (GA_j - GB_i): tangents, open under any box)
             dX, dC = PairListPull.apply(W, GA, GB, plist, want_x, want_c, _pull_dtype(ct, X, C, want_x, want_c))
-        return dW, _as(dX, X.dtype), _as(dC, C.dtype), None, None, None, None, None
+        return dW, _as(dX, X.dtype), _as(dC, C.dtype), None, None, None, None, None, None
 
 
 class PairListDot(torch.autograd.Function):
@@ -395,27 +398,27 @@ class PairListDot(torch.autograd.Function):
     dtype.  ``box``: the second factor is its minimum image; V - Y is never wrapped (see ``PairListDist``)."""
 
     @staticmethod
-    def forward(ctx, V, Y, X, C, plist, box=None):
+    def forward(ctx, V, Y, X, C, plist, box=None, near=False):
         ct = _pair_dtype(V, Y, X, C)
         out = K.pair_list_dist(_widened(X, ct), _widened(C, ct), _tables(plist, X), K.PAIR_DOT, _widened(V, ct),
-                               _widened(Y, ct), **_box_kw(box, ct))
-        ctx.plist, ctx.box = plist, box
+                               _widened(Y, ct), **_box_kw(box, ct, near))
+        ctx.plist, ctx.box, ctx.near = plist, box, bool(near)
         ctx.save_for_backward(V, Y, X, C)
         return out
 
     @staticmethod
     def backward(ctx, H):
         V, Y, X, C = ctx.saved_tensors
-        plist, box = ctx.plist, ctx.box
+        plist, box, near = ctx.plist, ctx.box, ctx.near
         need = ctx.needs_input_grad
         dV = dY = dX = dC = None
         ct = _pair_dtype(H, V, Y, X, C)
         if need[0] or need[1]:
             dV, dY = PairListPull.apply(H, X, C, plist, need[0], need[1], _pull_dtype(ct, V, Y, need[0], need[1]),
-                                        box)
+                                        box, near)
         if need[2] or need[3]:  # (sums of H (V_j - Y_i): tangents, open under any box)
             dX, dC = PairListPull.apply(H, V, Y, plist, need[2], need[3], _pull_dtype(ct, X, C, need[2], need[3]))
-        return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype), None, None
+        return _as(dV, V.dtype), _as(dY, Y.dtype), _as(dX, X.dtype), _as(dC, C.dtype), None, None, None
 
 
 # ------------------------------------------------------------------ Gaussian radial basis (K10)

@@ -20,16 +20,51 @@ orthorhombic minimum image component by component, bit for bit.  What it guarant
   for any lower-triangular cell (no "reduced" condition on the skews);
 * it is the true minimum image whenever that is shorter than ``safe_radius = min(ax, by, cz) / 2``;
 * beyond ``safe_radius`` it is still a periodic image, never shorter than the minimum: a cutoff list with
-  ``cutoff <= safe_radius`` is exact.  An exact minimum image beyond that radius is not built.
+  ``cutoff <= safe_radius`` is exact.
 
 This is what OpenMM and GROMACS do inside their cutoffs, and the "shorter than half the cell" condition that
-``make_whole`` documents for bonds.  Not built under a cell: ``gb_feat`` / ``qp.jaxfeat.gb_subfeat`` (K4), ``comm=``
-(frames sharded over ranks), gradients with respect to the cell.
+``make_whole`` documents for bonds.
+
+THE NEAREST IMAGE, ``Cell(vectors, images="nearest")``.  In the cells solvated systems are run in, ``safe_radius`` is
+well short of where the minimum image is well defined (half the shortest lattice vector); in float64, for cells of
+image distance d and 2e5 random displacements each:
+
+    cell                                    safe_radius   half the shortest      true minimum image below d/2
+                                                          lattice vector         where the brick image is not it
+    rhombic dodecahedron, square form         0.354 d        0.5 d                   11.7 %
+    rhombic dodecahedron, hexagonal form      0.408 d        0.5 d                    7.3 %
+    truncated octahedron                      0.408 d        0.5 d                    5.1 %
+
+The nearest form starts from the brick image and takes the shortest of its 27 translates ``d + i a + j b + k c``,
+``i, j, k`` in {-1, 0, 1}, by squared length.  The candidates are visited in one fixed order -- (0, 0, 0) first, then
+k = -1, 0, 1 outermost, j inside it, i innermost -- and a candidate replaces the best so far only if it is strictly
+shorter: a tie keeps the earlier one (the brick image before all others), and the choice is deterministic.  A brick
+image no longer than ``safe_radius`` is the answer already and the search is skipped, with the same bits
+(``csrc/aggf_common.h``, ``nearest_image``).  What it guarantees:
+
+* for a REDUCED cell -- ``|bx| <= ax/2``, ``|cx| <= ax/2``, ``|cy| <= by/2``, the GROMACS condition; equality allowed --
+  the result is the true minimum image whenever that image is shorter than ``image_radius``, half the length of the
+  shortest of the 26 lattice vectors ``i a + j b + k c``;
+* beyond ``image_radius`` it is a periodic image, never longer than the brick image;
+* with zero off-diagonal entries it is the orthorhombic minimum image bit for bit, and wherever the brick image is
+  within ``safe_radius`` it is the brick image bit for bit.
+
+The image is a locally constant choice, so gradients are those of the brick form with that image, to any order.  It
+is used by ``pair_distances``, ``distances_in_box``, ``min_distances``, ``PairList.from_cutoff`` and the map-validation
+functions; ``guess_pairwise_constraints`` and ``make_whole`` accept such a cell and run their brick forms (they
+measure bonds and rigid pairs, which must be shorter than ``safe_radius``, where the two images coincide).
+
+Not built under a cell: ``gb_feat`` / ``qp.jaxfeat.gb_subfeat`` (K4), ``comm=`` (frames sharded over ranks), gradients
+with respect to the cell; an exact minimum image beyond ``image_radius``; the nearest image of a cell that is not
+reduced.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
+
+
+REDUCED_SLACK = 1e-6  # relative: the roundings of a float32 cell on the conditions of a reduced cell
 
 
 class Cell:
@@ -42,10 +77,18 @@ class Cell:
     whose diagonal entry is not positive and finite, or whose lower off-diagonal entry is not finite, comes out NaN
     (image counts 0) and no other frame.  The cell is a constant: one that requires a gradient is refused.
 
+    ``images``: ``"brick"`` (the default: every displacement is its brick image) or ``"nearest"`` (the shortest of the
+    brick image's 27 translates: the module's text).  A host cell with ``images="nearest"`` must be reduced,
+    ``|bx| <= ax/2``, ``|cx| <= ax/2``, ``|cy| <= by/2`` (``ValueError``; equality is allowed, with a relative slack of
+    1e-6 for a cell that was stored in float32 or converted from angles); a cell on a GPU is taken as it is.
+
     A class, not a raw array, because a raw (3, 3) array given as ``box=`` to three frames already means one
     orthorhombic box per frame."""
 
-    def __init__(self, vectors):
+    def __init__(self, vectors, images: str = "brick"):
+        if images not in ("brick", "nearest"):
+            raise ValueError(f'Cell: images must be "brick" or "nearest"; got {images!r}')
+        self._images = images
         if isinstance(vectors, Cell):
             vectors = vectors.vectors
         if isinstance(vectors, torch.Tensor):
@@ -70,14 +113,23 @@ class Cell:
                                  "b = (bx, by, 0), c = (cx, cy, cz); an upper-triangular entry is not zero")
             if not bool((torch.diagonal(v, dim1=-2, dim2=-1) > 0).all()):
                 raise ValueError("Cell: the diagonal entries ax, by, cz must be positive and finite")
+            if images == "nearest":
+                # (equality is the rule in the standard cells -- the dodecahedron has cx = ax/2 -- and a cell that
+                # went through float32 or through lengths and angles misses it by a rounding: REDUCED_SLACK)
+                ax, by = v[..., 0, 0] * (1 + REDUCED_SLACK), v[..., 1, 1] * (1 + REDUCED_SLACK)
+                if not bool(((v[..., 1, 0].abs() <= ax / 2) & (v[..., 2, 0].abs() <= ax / 2)
+                             & (v[..., 2, 1].abs() <= by / 2)).all()):
+                    raise ValueError('Cell: images="nearest" needs a reduced cell: |bx| <= ax/2, |cx| <= ax/2 and '
+                                     "|cy| <= by/2 (add multiples of a to b, and of a and b to c, until they hold)")
         self._v = v.detach()
 
     @classmethod
-    def from_lengths_angles(cls, lengths, angles_deg) -> "Cell":
+    def from_lengths_angles(cls, lengths, angles_deg, images: str = "brick") -> "Cell":
         """The cell of edge lengths (A, B, C) and angles (alpha, beta, gamma) in degrees, (3,) or (n_steps, 3) each
         (alpha between b and c, beta between a and c, gamma between a and b), by the standard conversion in float64:
         a = (A, 0, 0), b = (B cos gamma, B sin gamma, 0), cx = C cos beta, cy = C (cos alpha - cos beta cos gamma) /
-        sin gamma, cz = sqrt(C^2 - cx^2 - cy^2).  An angle of exactly 90 degrees gives an exact zero."""
+        sin gamma, cz = sqrt(C^2 - cx^2 - cy^2).  An angle of exactly 90 degrees gives an exact zero.  ``images``: as in
+        ``Cell``."""
         try:
             L = np.asarray(lengths.detach().cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.float64)
             A = np.asarray(angles_deg.detach().cpu() if isinstance(angles_deg, torch.Tensor) else angles_deg,
@@ -99,7 +151,7 @@ class Cell:
             v[..., 2, 0] = L[..., 2] * cb
             v[..., 2, 1] = L[..., 2] * (ca - cb * cg) / sg
             v[..., 2, 2] = np.sqrt(L[..., 2] ** 2 - v[..., 2, 0] ** 2 - v[..., 2, 1] ** 2)
-        return cls(v)
+        return cls(v, images=images)
 
     @property
     def vectors(self) -> torch.Tensor:
@@ -124,11 +176,35 @@ class Cell:
         r = d.min() / 2
         return r if self._v.is_cuda else float(r)
 
+    @property
+    def images(self) -> str:
+        """``"brick"`` or ``"nearest"``: the image this cell gives a displacement."""
+        return self._images
+
+    @property
+    def nearest(self) -> bool:
+        return self._images == "nearest"
+
+    @property
+    def image_radius(self):
+        """Up to this length the cell's image is the true minimum image: ``safe_radius`` for ``"brick"``; for
+        ``"nearest"`` half the length of the shortest of the 26 lattice vectors ``i a + j b + k c``, ``i, j, k`` in
+        {-1, 0, 1}, over all frames.  A float for a host cell, a 0-d tensor for a cell on a GPU (no synchronisation)."""
+        if not self.nearest:
+            return self.safe_radius
+        if self._v.numel() == 0:
+            return float("inf") if not self._v.is_cuda else torch.full((), float("inf"), device=self._v.device)
+        idx = torch.arange(27, device=self._v.device)
+        ijk = torch.stack([idx % 3 - 1, idx // 3 % 3 - 1, idx // 9 - 1], dim=1).to(self._v.dtype)
+        lengths = torch.linalg.vector_norm(ijk @ self._v, dim=-1)  # (the combination (0, 0, 0) has length 0: left out)
+        r = torch.where(lengths > 0, lengths, torch.full_like(lengths, float("inf"))).min() / 2
+        return r if self._v.is_cuda else float(r)
+
     def take(self, frames) -> "Cell":
         """The cell of the frames ``frames`` (an index array): itself unless it is per frame."""
         if not self.is_per_frame:
             return self
-        return Cell(self._v[torch.as_tensor(np.asarray(frames), device=self._v.device)])
+        return Cell(self._v[torch.as_tensor(np.asarray(frames), device=self._v.device)], images=self._images)
 
     def rows(self, n_steps: int) -> torch.Tensor:
         """(n_steps, 9): the row-major matrix of every frame -- the form the kernels and host bodies take (a constant
@@ -142,12 +218,41 @@ class Cell:
         return self._v.reshape(1, 9).expand(n_steps, 9)
 
     def __repr__(self) -> str:
-        return f"Cell({'per frame, ' if self.is_per_frame else ''}vectors={self._v.tolist() if self._v.numel() <= 9 else '...'})"
+        return (f"Cell({'per frame, ' if self.is_per_frame else ''}"
+                f"vectors={self._v.tolist() if self._v.numel() <= 9 else '...'}"
+                f"{', images=' + repr(self._images) if self.nearest else ''})")
 
 
 def is_cell_rows(box) -> bool:
     """Whether a normalised box (``jaxutil._as_box``) is the (n_steps, 9) form of a ``Cell``."""
     return box is not None and box.dim() == 2 and box.shape[1] == 9
+
+
+def is_nearest(box) -> bool:
+    """Whether ``box`` as a caller gave it is a ``Cell`` with ``images="nearest"``."""
+    return isinstance(box, Cell) and box.nearest
+
+
+def nearest_of(d0, d1, d2, ax, bx, by, cx, cy, cz):
+    """The nearest image of the BRICK image (d0, d1, d2) in plain torch (the host bodies): the shortest of its 27
+    translates by squared length, (0, 0, 0) first, then k outermost, j, i innermost from -1 to 1, replaced only by a
+    strictly shorter one -- the search of ``nearest_image`` (csrc/aggf_common.h), unpruned (pruning changes no bit).
+    The choice is made on detached values; the result is the chosen translate of the given tensors."""
+    with torch.no_grad():
+        best = d0 * d0 + d1 * d1 + d2 * d2
+        pick = torch.zeros(best.shape + (3,), dtype=best.dtype, device=best.device)
+        for k in (-1, 0, 1):
+            for j in (-1, 0, 1):
+                for i in (-1, 0, 1):
+                    if i == j == k == 0:
+                        continue
+                    x, y, z = d0 + k * cx + j * bx + i * ax, d1 + k * cy + j * by, d2 + k * cz
+                    q = x * x + y * y + z * z
+                    shorter = q < best
+                    best = torch.where(shorter, q, best)
+                    pick = torch.where(shorter.unsqueeze(-1), torch.tensor([i, j, k], dtype=best.dtype, device=best.device), pick)
+        i, j, k = pick[..., 0], pick[..., 1], pick[..., 2]
+    return d0 + k * cx + j * bx + i * ax, d1 + k * cy + j * by, d2 + k * cz
 
 
 def refuse_cell(box, who: str) -> None:

@@ -1118,12 +1118,13 @@ def pair_pool_term(var_r: torch.Tensor, mean_r: torch.Tensor, mean: torch.Tensor
 
 
 def gauss_pair_forces(x: torch.Tensor, offset: float, width: float, want_forces: bool = True,
-                      want_energies: bool = False, box: Optional[torch.Tensor] = None):
+                      want_energies: bool = False, box: Optional[torch.Tensor] = None, near: bool = False):
     """(G (T, n, 3) or None, E (T,) or None) in x's dtype for one squared-distance Gaussian; see aggf_gauss_pair_forces.
-    ``box`` ((3,), (T, 3) or the (T, 9) rows of a cell, in x's dtype): every r_i - r_j is its image under it."""
+    ``box`` ((3,), (T, 3) or the (T, 9) rows of a cell, in x's dtype): every r_i - r_j is its image under it.  ``near``
+    (with the rows of a cell): the nearest image instead of the brick image (aggf_gauss_pair_forces_cell)."""
     l = lib()
     T, n, _ = x.shape
-    stride = 0 if box is None else _box_arg("gauss_pair_forces", box, x, cell=True)
+    stride = 0 if box is None else _box_arg("gauss_pair_forces", box, x, cell=True, near=near)
     G = torch.empty_like(x) if want_forces else None
     E = torch.empty(T, dtype=x.dtype, device=x.device) if want_energies else None
     if x.numel() == 0:
@@ -1131,23 +1132,33 @@ def gauss_pair_forces(x: torch.Tensor, offset: float, width: float, want_forces:
     need = l.aggf_gauss_pair_forces_workspace_bytes(T, n) if want_energies else 0
     ws = workspace(need, x.device, "mapval") if want_energies else None
     with _timed("gauss_forces"):
+        if near:
+            check(l.aggf_gauss_pair_forces_cell(ptr(x), T, n, dtype_code(x.dtype), float(offset), float(width), ptr(box),
+                                                ptr(G), ptr(E), ptr(ws), need, stream_ptr(), IMAGES_NEAREST),
+                  "aggf_gauss_pair_forces_cell")
+            return G, E
         check(l.aggf_gauss_pair_forces(ptr(x), T, n, dtype_code(x.dtype), float(offset), float(width), ptr(box), stride,
                                        ptr(G), ptr(E), ptr(ws), need, stream_ptr()), "aggf_gauss_pair_forces")
     return G, E
 
 
 def gauss_proj(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float,
-               box: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """(S,) float64: sum over frames and sites of F . G_s for every offset; see aggf_gauss_proj.  ``box``: as
-    ``gauss_pair_forces``."""
+               box: Optional[torch.Tensor] = None, near: bool = False) -> torch.Tensor:
+    """(S,) float64: sum over frames and sites of F . G_s for every offset; see aggf_gauss_proj.  ``box``, ``near``:
+    as ``gauss_pair_forces`` (aggf_gauss_proj_cell)."""
     l = lib()
     T, n, _ = x.shape
-    stride = 0 if box is None else _box_arg("gauss_proj", box, x, cell=True)
+    stride = 0 if box is None else _box_arg("gauss_proj", box, x, cell=True, near=near)
     S = offsets.numel()
     out = torch.empty(S, dtype=torch.float64, device=x.device)
     need = l.aggf_gauss_proj_workspace_bytes(T, n, S)
     ws = workspace(need, x.device, "mapval")
     with _timed("gauss_proj"):
+        if near:
+            check(l.aggf_gauss_proj_cell(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
+                                         float(width), ptr(box), ptr(out), ptr(ws), need, stream_ptr(), IMAGES_NEAREST),
+                  "aggf_gauss_proj_cell")
+            return out
         check(l.aggf_gauss_proj(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
                                 float(width), ptr(box), stride, ptr(out), ptr(ws), need, stream_ptr()),
               "aggf_gauss_proj")
@@ -1155,18 +1166,23 @@ def gauss_proj(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: f
 
 
 def gauss_shift(x: torch.Tensor, f: torch.Tensor, offsets: torch.Tensor, width: float,
-                box: Optional[torch.Tensor] = None):
-    """((S,), (S,)) float64: sum F . G_s and sum |G_s|^2 for every offset, one pass; see aggf_gauss_shift.  ``box``:
-    as ``gauss_pair_forces``."""
+                box: Optional[torch.Tensor] = None, near: bool = False):
+    """((S,), (S,)) float64: sum F . G_s and sum |G_s|^2 for every offset, one pass; see aggf_gauss_shift.  ``box``,
+    ``near``: as ``gauss_pair_forces`` (aggf_gauss_shift_cell)."""
     l = lib()
     T, n, _ = x.shape
-    stride = 0 if box is None else _box_arg("gauss_shift", box, x, cell=True)
+    stride = 0 if box is None else _box_arg("gauss_shift", box, x, cell=True, near=near)
     S = offsets.numel()
     ip = torch.empty(S, dtype=torch.float64, device=x.device)
     gsq = torch.empty(S, dtype=torch.float64, device=x.device)
     need = l.aggf_gauss_shift_workspace_bytes(T, n, S)
     ws = workspace(need, x.device, "mapval")
     with _timed("gauss_shift"):
+        if near:
+            check(l.aggf_gauss_shift_cell(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets),
+                                          S, float(width), ptr(box), ptr(ip), ptr(gsq), ptr(ws), need, stream_ptr(), IMAGES_NEAREST),
+                  "aggf_gauss_shift_cell")
+            return ip, gsq
         check(l.aggf_gauss_shift(ptr(x), dtype_code(x.dtype), ptr(f), dtype_code(f.dtype), T, n, ptr(offsets), S,
                                  float(width), ptr(box), stride, ptr(ip), ptr(gsq), ptr(ws), need, stream_ptr()),
               "aggf_gauss_shift")
@@ -1248,6 +1264,7 @@ def trjdot_frames_outer(g: torch.Tensor, p: torch.Tensor, out_dtype: torch.dtype
 
 # ------------------------------------------------------------------ K9 pair distances (aggforce_amd/_autograd.py)
 PAIR_DIST, PAIR_SQDIST, PAIR_DOT = 0, 1, 2
+IMAGES_BRICK, IMAGES_NEAREST = 0, 1  # AGGF_IMAGES_*: the image selector of the ``_cell`` entries
 
 
 def _pair_sites(name: str, x: torch.Tensor, c: torch.Tensor):
@@ -1330,11 +1347,15 @@ def _pair_list_sites(name: str, x: torch.Tensor, c: torch.Tensor, tab: PairTable
     return T, m, n, tab.n_pairs
 
 
-def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor, cell: bool = False) -> int:
+def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor, cell: bool = False, near: bool = False) -> int:
     """The element stride between the frames of ``box`` (the ``box_stride`` of include/aggf.h): 3 for (T, 3), 0 for
     (3,); a contiguous tensor in the dtype and on the device of ``x``.  ``cell``: the entry also takes (T, 9), a
-    row-major 3 x 3 triclinic cell per frame (``pbc.Cell.rows``), stride 9; the K4 entries do not."""
+    row-major 3 x 3 triclinic cell per frame (``pbc.Cell.rows``), stride 9; the K4 entries do not.  ``near`` (the
+    nearest image of a cell, the ``_cell`` entries with AGGF_IMAGES_NEAREST): ``box`` must be those (T, 9) rows."""
     T = x.shape[0]
+    if near and (not isinstance(box, torch.Tensor) or tuple(box.shape) != (T, 9)):
+        raise ValueError(f"{name}: the nearest image needs the ({T}, 9) rows of a cell; got "
+                         f"{tuple(box.shape) if hasattr(box, 'shape') else type(box)}")
     shapes = ((3,), (T, 3), (T, 9)) if cell else ((3,), (T, 3))
     if (not isinstance(box, torch.Tensor) or box.dtype != x.dtype or box.device != x.device or not box.is_contiguous()
             or tuple(box.shape) not in shapes):
@@ -1347,13 +1368,14 @@ def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor, cell: bool = False) 
 
 def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int = PAIR_DIST,
                    v: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
-                   box: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   box: Optional[torch.Tensor] = None, near: bool = False) -> torch.Tensor:
     """(T, P) in the operands' dtype over u[t,p] = x[t,j_p] - c[t,i_p] (aggf_pair_list_dist): |u|, u.u or
     (v[t,j_p] - y[t,i_p]).u by ``mode``, as ``pair_dist``.  ``box`` ((3,) or (T, 3), the operands' dtype): u is its
     minimum image under that orthorhombic box (aggf_pair_list_dist_pbc); v - y is never wrapped.  (T, 9): the rows of
-    a triclinic cell (``pbc.Cell.rows``), u is its brick image."""
+    a triclinic cell (``pbc.Cell.rows``), u is its brick image or, with ``near``, its nearest image
+    (aggf_pair_list_dist_cell)."""
     T, m, n, P = _pair_list_sites("pair_list_dist", x, c, tab)
-    stride = None if box is None else _box_arg("pair_list_dist", box, x, cell=True)
+    stride = None if box is None else _box_arg("pair_list_dist", box, x, cell=True, near=near)
     if mode not in (PAIR_DIST, PAIR_SQDIST, PAIR_DOT):
         raise ValueError(f"pair_list_dist: mode {mode}")
     if mode == PAIR_DOT:
@@ -1365,7 +1387,11 @@ def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int 
     if out.numel() == 0:
         return out
     with _timed("pair_list_dist"):
-        if box is None:
+        if near:
+            check(lib().aggf_pair_list_dist_cell(ptr(x), ptr(c), ptr(v), ptr(y), ptr(tab.pairs), T, m, n, P,
+                                                 dtype_code(x.dtype), mode, ptr(box), ptr(out), stream_ptr(), IMAGES_NEAREST),
+                  "aggf_pair_list_dist_cell")
+        elif box is None:
             check(lib().aggf_pair_list_dist(ptr(x), ptr(c), ptr(v), ptr(y), ptr(tab.pairs), T, m, n, P,
                                             dtype_code(x.dtype), mode, ptr(out), stream_ptr()), "aggf_pair_list_dist")
         else:
@@ -1377,13 +1403,15 @@ def pair_list_dist(x: torch.Tensor, c: torch.Tensor, tab: PairTables, mode: int 
 
 def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairTables,
                    dv: Optional[torch.Tensor] = None, want_a: bool = True, want_b: bool = True,
-                   out_dtype: Optional[torch.dtype] = None, box: Optional[torch.Tensor] = None):
+                   out_dtype: Optional[torch.dtype] = None, box: Optional[torch.Tensor] = None,
+                   near: bool = False):
     """(A, B): A[t,j,:] = sum_{p: j_p = j} w_p u_p (T, n, 3) and B[t,i,:] = -sum_{p: i_p = i} w_p u_p (T, m, 3) over
     u[t,p] = x[t,j_p] - c[t,i_p], with the weights w (T, P) or, given ``dv``, (dv > 0 ? w / dv : 0)
     (aggf_pair_list_pull).  An output that is not wanted is None and costs nothing.  All operands share a dtype at
-    least as wide as out_dtype (default: theirs).  ``box``: as ``pair_list_dist`` (aggf_pair_list_pull_pbc)."""
+    least as wide as out_dtype (default: theirs).  ``box``, ``near``: as ``pair_list_dist`` (aggf_pair_list_pull_pbc,
+    aggf_pair_list_pull_cell)."""
     T, m, n, P = _pair_list_sites("pair_list_pull", x, c, tab)
-    stride = None if box is None else _box_arg("pair_list_pull", box, x, cell=True)
+    stride = None if box is None else _box_arg("pair_list_pull", box, x, cell=True, near=near)
     out_dtype = out_dtype or x.dtype
     for name, arr in (("w", w), ("dv", dv)):
         if arr is not None and (tuple(arr.shape) != (T, P) or arr.dtype != x.dtype or not arr.is_contiguous()):
@@ -1398,7 +1426,12 @@ def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairT
     if not (want_a or want_b):
         return None, None
     with _timed("pair_list_pull"):
-        if box is None:
+        if near:
+            check(lib().aggf_pair_list_pull_cell(ptr(w), ptr(dv), ptr(x), ptr(c), ptr(tab.pairs), ptr(tab.a_ptr),
+                                                 ptr(tab.a_idx), ptr(tab.b_ptr), ptr(tab.b_idx), tab.max_deg_a,
+                                                 tab.max_deg_b, T, m, n, P, dtype_code(x.dtype), ptr(box), ptr(a), ptr(b),
+                                                 dtype_code(out_dtype), stream_ptr(), IMAGES_NEAREST), "aggf_pair_list_pull_cell")
+        elif box is None:
             check(lib().aggf_pair_list_pull(ptr(w), ptr(dv), ptr(x), ptr(c), ptr(tab.pairs), ptr(tab.a_ptr),
                                             ptr(tab.a_idx), ptr(tab.b_ptr), ptr(tab.b_idx), tab.max_deg_a,
                                             tab.max_deg_b, T, m, n, P, dtype_code(x.dtype), ptr(a), ptr(b),
@@ -1412,12 +1445,13 @@ def pair_list_pull(w: torch.Tensor, x: torch.Tensor, c: torch.Tensor, tab: PairT
     return a, b
 
 
-def pair_min(x: torch.Tensor, c: torch.Tensor, square: bool = False, box: Optional[torch.Tensor] = None) -> torch.Tensor:
+def pair_min(x: torch.Tensor, c: torch.Tensor, square: bool = False, box: Optional[torch.Tensor] = None,
+             near: bool = False) -> torch.Tensor:
     """(m, n) in the operands' dtype: out[i,j] = min_t |x[t,j] - c[t,i]| (``square``: squared), the minimum image
-    under ``box`` if given (aggf_pair_min, K9e).  A NaN distance makes its pair NaN; without frames every minimum is
-    +inf (the empty minimum)."""
+    under ``box`` if given (aggf_pair_min, K9e; ``near`` with the rows of a cell: the nearest image,
+    aggf_pair_min_cell).  A NaN distance makes its pair NaN; without frames every minimum is +inf (the empty minimum)."""
     T, m, n = _pair_sites("pair_min", x, c)
-    stride = 0 if box is None else _box_arg("pair_min", box, x, cell=True)
+    stride = 0 if box is None else _box_arg("pair_min", box, x, cell=True, near=near)
     if T == 0:
         return torch.full((m, n), float("inf"), dtype=x.dtype, device=x.device)
     out = torch.empty((m, n), dtype=x.dtype, device=x.device)
@@ -1427,6 +1461,10 @@ def pair_min(x: torch.Tensor, c: torch.Tensor, square: bool = False, box: Option
     need = l.aggf_pair_min_workspace_bytes(T, m, n, dtype_code(x.dtype))
     ws = workspace(need, x.device, "pairmin") if need else None
     with _timed("pair_min"):
+        if near:
+            check(l.aggf_pair_min_cell(ptr(x), ptr(c), T, m, n, dtype_code(x.dtype), ptr(box), int(bool(square)),
+                                       ptr(out), ptr(ws), need, stream_ptr(), IMAGES_NEAREST), "aggf_pair_min_cell")
+            return out
         check(l.aggf_pair_min(ptr(x), ptr(c), T, m, n, dtype_code(x.dtype), ptr(box), stride, int(bool(square)),
                               ptr(out), ptr(ws), need, stream_ptr()), "aggf_pair_min")
     return out

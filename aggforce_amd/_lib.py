@@ -89,6 +89,10 @@ PROTOTYPES = {
                                           C.c_int, _vp, _i32, _vp, _vp, C.c_int, _vp]),
     "aggf_pair_min_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
     "aggf_pair_min": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, _i32, C.c_int, _vp, _vp, _sz, _vp]),
+    "aggf_pair_list_dist_cell": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
+    "aggf_pair_list_pull_cell": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64,
+                                           C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int]),
+    "aggf_pair_min_cell": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, C.c_int, _vp, _vp, _sz, _vp, C.c_int]),
     "aggf_make_whole_lds_max_sites": (_i32, []),
     "aggf_make_whole_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
     "aggf_make_whole": (C.c_int, [_vp, _i64, _i32, C.c_int, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _sz, C.c_int, _vp]),
@@ -128,6 +132,10 @@ PROTOTYPES = {
     "aggf_gauss_shift_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "aggf_gauss_shift": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _i32, _vp, _vp, _vp, _sz,
                                    _vp]),
+    "aggf_gauss_pair_forces_cell": (C.c_int, [_vp, _i64, _i32, C.c_int, _dbl, _dbl, _vp, _vp, _vp, _vp, _sz, _vp, C.c_int]),
+    "aggf_gauss_proj_cell": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _vp, _vp, _sz, _vp, C.c_int]),
+    "aggf_gauss_shift_cell": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _sz,
+                                        _vp, C.c_int]),
     "aggf_dot_workspace_bytes": (_sz, []),
     "aggf_dot": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _vp, _vp, _sz, _vp]),
     "aggf_synth_normal": (C.c_int, [_vp, _i64, _i32, C.c_int, _u64, _i64, _dbl, _dbl, _dbl, _vp]),

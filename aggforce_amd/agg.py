@@ -125,7 +125,8 @@ def project_forces(
     measures minimum-image distances (``guess_pairwise_constraints(..., box=)``) and so keeps the rigid pairs
     that straddle a face of the cell in some frames; with explicit constraints or None its shape is checked and
     it is otherwise ignored.  A ``pbc.Cell`` stands for a triclinic cell (brick images, exact up to
-    ``Cell.safe_radius``: ``pbc``), here and in ``bonds``; with ``comm=`` a ``Cell`` is refused.  On its own it
+    ``Cell.safe_radius``: ``pbc``; a cell with ``images="nearest"`` runs the same brick forms here, since bonds and
+    rigid pairs are shorter than that radius), here and in ``bonds``; with ``comm=`` a ``Cell`` is refused.  On its own it
     changes nothing else: mapped coordinates are still ``coord_map``
     applied to the coordinates as given -- exact for slice maps, off by a box length for averaging maps of
     molecules that the wrap has split (pass ``bonds``) -- and a featuriser gets its box through its own binding

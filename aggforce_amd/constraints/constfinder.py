@@ -41,7 +41,8 @@ def guess_pairwise_constraints(xyz, cross_xyz: Union[None, np.ndarray] = None, t
     ``box`` may be a ``pbc.Cell`` (a triclinic cell): every distance is then that of the brick image (``pbc``), in
     float64 on the triclinic form of K6 -- the minimum-image distance for pairs closer than ``cell.safe_radius``,
     which every rigid pair of a molecule is.  A cell with a bad frame raises ValueError, as bad lengths do; with
-    ``comm`` a ``Cell`` is refused (not built).
+    ``comm`` a ``Cell`` is refused (not built).  A cell with ``images="nearest"`` is accepted and measured in the
+    same brick form: a rigid pair is shorter than ``safe_radius``, where the two images coincide.
     """
     lengths = None
     if box is not None:

@@ -279,8 +279,68 @@ __device__ __forceinline__ void brick_image(T& d0, T& d1, T& d2, const CellFrame
   const T ka = cell_rint(d0 * h.iax);
   d0 = cell_fma(-ka, h.ax, d0);
 }
-// the form of a kernel body: no box, an orthorhombic box (min_image), a triclinic cell (brick_image)
-constexpr int CELL_OPEN = 0, CELL_BOX = 1, CELL_TRI = 2;
+// ---- NEAREST IMAGE.  The brick image, then the shortest of its 27 translates d + i a + j b + k c, i, j, k in {-1, 0, 1},
+// by squared length (cell_sq).  The candidates are visited in one fixed order: (0, 0, 0) -- the brick image itself --
+// first, then k (of c) = -1, 0, 1 outermost, j (of b) inside it, i (of a) innermost, each from -1 to 1; a candidate
+// replaces the best so far only if it is STRICTLY shorter, so a tie keeps the earlier one (the brick image before all)
+// and the choice is a function of d alone.  A translate is formed like the brick image, c first:
+//   x = fma(i, ax, fma(j, bx, fma(k, cx, d0)));  y = fma(j, by, fma(k, cy, d1));  z = fma(k, cz, d2)
+// (a zero count leaves the component as it is).  For a REDUCED cell (|bx| <= ax/2, |cx| <= ax/2, |cy| <= by/2) the
+// result is the true minimum image whenever that image is shorter than half the shortest of the 26 lattice vectors
+// i a + j b + k c (pbc.Cell.image_radius); beyond that it is a periodic image that is never longer than the brick image.
+// PRUNING: every lattice vector of a lower-triangular cell is at least min(ax, by, cz) long, so a brick image with
+// |d|^2 <= min(ax, by, cz)^2 / 4 has no strictly shorter translate and the search is skipped: the same bits as the full
+// search (a translate could round below the brick image only for a d that sits on a tie at exactly that length).
+// A bad frame is NaN as in the brick form: every comparison with NaN is false, the NaN brick image stays.
+__device__ __forceinline__ float cell_min(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double cell_min(double a, double b) { return __builtin_fmin(a, b); }
+template <typename T>
+__device__ __forceinline__ T cell_sq(T e0, T e1, T e2) {
+#pragma clang fp contract(off)
+  return cell_fma(e2, e2, cell_fma(e1, e1, e0 * e0));
+}
+// d + count * step for a count in {-1, 0, 1} that is a constant once the search is unrolled
+template <typename T>
+__device__ __forceinline__ T cell_step(int count, T step, T d) {
+  return count == 0 ? d : cell_fma((T)count, step, d);
+}
+template <typename T>
+__device__ __forceinline__ void nearest_image(T& d0, T& d1, T& d2, const CellFrame<T>& h) {
+#pragma clang fp contract(off)
+  brick_image(d0, d1, d2, h);
+  const T m = cell_min(cell_min(h.ax, h.by), h.cz);
+  T best = cell_sq(d0, d1, d2);
+  if (best <= (T)0.25 * (m * m)) return;
+  T b0 = d0, b1 = d1, b2 = d2;
+#pragma unroll
+  for (int k = -1; k <= 1; ++k) {
+    const T z = cell_step(k, h.cz, d2), yk = cell_step(k, h.cy, d1), xk = cell_step(k, h.cx, d0);
+#pragma unroll
+    for (int j = -1; j <= 1; ++j) {
+      const T y = cell_step(j, h.by, yk), xj = cell_step(j, h.bx, xk);
+#pragma unroll
+      for (int i = -1; i <= 1; ++i) {
+        if (i == 0 && j == 0 && k == 0) continue;
+        const T x = cell_step(i, h.ax, xj);
+        const T q = cell_sq(x, y, z);
+        const bool shorter = q < best;
+        best = shorter ? q : best, b0 = shorter ? x : b0, b1 = shorter ? y : b1, b2 = shorter ? z : b2;
+      }
+    }
+  }
+  d0 = b0, d1 = b1, d2 = b2;
+}
+// the form of a kernel body: no box, an orthorhombic box (min_image), a triclinic cell (brick_image), a triclinic cell
+// with the nearest image (nearest_image; the same nine numbers per frame as CELL_TRI)
+constexpr int CELL_OPEN = 0, CELL_BOX = 1, CELL_TRI = 2, CELL_NEAR = 3;
+// the image of a displacement under a cell form that holds a CellFrame
+template <int CELL, typename T>
+__device__ __forceinline__ void cell_image(T& d0, T& d1, T& d2, const CellFrame<T>& h) {
+  if (CELL == CELL_NEAR)
+    nearest_image(d0, d1, d2, h);
+  else
+    brick_image(d0, d1, d2, h);
+}
 
 // ---- Philox4x32-10 (Salmon et al., SC'11): counter = 64-bit quad index, key = seed ----
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {

@@ -24,6 +24,12 @@
 // CellFrame per frame and takes the brick image (aggf_common.h); the lengths of an orthorhombic box are loaded as a
 // cell without off-diagonal entries, which is min_image bit for bit (fma(-k, 0, d) == d).  A frame whose box or cell
 // is bad (box_lengths, cell_good) has NaN images: its G and E are NaN, and so is every sample of a fused reduction.
+// The nearest-image forms (a further template argument CELL_NEAR on overloads of the three kernels; aggf_*_cell with
+// AGGF_IMAGES_NEAREST) take the same (T, 9) cells and replace brick_image by nearest_image.  The kernels' text is in
+// aggf_mapval_kernels.inc, included twice, so that the open and periodic kernels are compiled from the tokens they have
+// always had: their names, instructions and bits are unchanged.  The products of the sums (u = d . (F_i - F_j), c d) are
+// fused as the compiler chooses per instantiation, so the nearest form's sums agree with the brick form's only to
+// rounding even where the two images are the same numbers (K9's agree bit for bit).
 #include "aggf_common.h"
 
 namespace aggf {
@@ -100,77 +106,17 @@ __device__ __forceinline__ void pair_of(int64_t p, int64_t n, int64_t* pi, int64
   *pj = i + 1 + (p - pair_row_start(i, n));
 }
 
-// ---- one offset: G (T, n, 3) and per-(frame, site block) energy partials.  Thread = (frame, site i); a workgroup
-// holds `fpb` frames x `iblk` sites (n <= 256: whole frames, 256 / n of them; else 1 frame x 256 sites) and stages
-// the j sites of its frames in LDS, MV_JT at a time.  PBC: a thread holds the cell of its own frame.
-template <typename TX, bool PBC>
-__global__ __launch_bounds__(MV_THREADS) void gauss_site_forces_kernel(const TX* __restrict__ X, int64_t T, int32_t n,
-                                                                        int32_t fpb, int32_t iblk, int32_t n_iblk,
-                                                                        int64_t n_blocks, TX offset, TX k, double scale,
-                                                                        TX* __restrict__ G, double* __restrict__ eslab,
-                                                                        const TX* __restrict__ box, int32_t bstride) {
-  __shared__ TX sx[MV_JT * 3];
-  __shared__ double se[MV_THREADS];
-  const int tid = threadIdx.x;
-  const int f = tid / iblk, il = tid - f * iblk;
-  for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-    const int64_t tb = b / n_iblk;
-    const int ib = (int)(b - tb * n_iblk);
-    const int64_t t0 = tb * fpb;
-    const int nf = (int)(T - t0 < fpb ? T - t0 : fpb);
-    const int64_t i = (int64_t)ib * iblk + il;
-    const bool active = f < nf && il < iblk && i < n;
-    const int64_t t = t0 + f;
-    TX r0 = 0, r1 = 0, r2 = 0;
-    if (active) {
-      const TX* xi = X + (t * n + i) * 3;
-      r0 = xi[0];
-      r1 = xi[1];
-      r2 = xi[2];
-    }
-    CellFrame<TX> h = {};
-    if (PBC && active) mv_cell(box, bstride, t, h);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, e = 0.0;
-    for (int64_t j0 = 0; j0 < n; j0 += MV_JT) {
-      const int jn = (int)(n - j0 < MV_JT ? n - j0 : MV_JT);
-      __syncthreads();
-      for (int m = tid; m < nf * jn * 3; m += MV_THREADS) {
-        const int ff = m / (jn * 3), q = m - ff * (jn * 3);
-        sx[m] = X[((t0 + ff) * n + j0) * 3 + q];
-      }
-      __syncthreads();
-      if (active) {
-        const TX* base = sx + f * jn * 3;
-        for (int j = 0; j < jn; ++j) {
-          TX d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
-          if (PBC) brick_image(d0, d1, d2, h);
-          const TX tt = sq_norm3(d0, d1, d2) - offset;
-          const TX g = Gauss<TX>::g(tt, k);
-          const double c = (double)(tt * g);
-          a0 += c * (double)d0;
-          a1 += c * (double)d1;
-          a2 += c * (double)d2;
-          e += (double)g;
-        }
-      }
-    }
-    if (G && active) {
-      TX* gi = G + (t * n + i) * 3;
-      gi[0] = (TX)(scale * a0);
-      gi[1] = (TX)(scale * a1);
-      gi[2] = (TX)(scale * a2);
-    }
-    if (eslab) {
-      se[tid] = active ? e : 0.0;
-      __syncthreads();
-      if (tid < nf) {
-        double s = 0.0;
-        for (int l = 0; l < iblk; ++l) s += se[tid * iblk + l];
-        eslab[(t0 + tid) * n_iblk + ib] = s;
-      }
-    }
-  }
-}
+#define AGGF_MV_FORM_PARAM
+#define AGGF_MV_IMAGE brick_image
+#include "aggf_mapval_kernels.inc"
+#undef AGGF_MV_FORM_PARAM
+#undef AGGF_MV_IMAGE
+// (the nearest-image forms: overloads with a further template argument, CELL_NEAR the only value instantiated)
+#define AGGF_MV_FORM_PARAM , int CELL
+#define AGGF_MV_IMAGE nearest_image
+#include "aggf_mapval_kernels.inc"
+#undef AGGF_MV_FORM_PARAM
+#undef AGGF_MV_IMAGE
 
 // E[t] = sum_ib eslab[t][ib], in order
 template <typename TX>
@@ -180,170 +126,6 @@ __global__ __launch_bounds__(256) void gauss_energy_finish_kernel(const double* 
     double s = 0.0;
     for (int ib = 0; ib < n_iblk; ++ib) s += eslab[t * n_iblk + ib];
     E[t] = (TX)s;
-  }
-}
-
-// ---- S offsets, projection, pair form.  Grid (K splits of the T * n (n - 1) / 2 entries, offset chunks).
-// slabs[k][s] = sum over split k of (x - o_s) g_s(x) u.  PBC: d is wrapped once per staged entry, under the cell of the
-// entry's own frame (a stage, and a split, span several frames).
-template <typename TX, typename TF, bool PBC>
-__global__ __launch_bounds__(MV_THREADS) void gauss_proj_kernel(const TX* __restrict__ X, const TF* __restrict__ F,
-                                                                 int64_t T, int32_t n,
-                                                                 const double* __restrict__ offsets, int64_t S,
-                                                                 double width, int64_t per_split,
-                                                                 double* __restrict__ slabs,
-                                                                 const TX* __restrict__ box, int32_t bstride) {
-  typedef typename Promote<TX, TF>::type C;
-  __shared__ C sx[MV_PL], su[MV_PL];
-  const int tid = threadIdx.x;
-  const int64_t P = (int64_t)n * (n - 1) / 2, n_entries = T * P;
-  const int64_t e_begin = (int64_t)blockIdx.x * per_split;
-  const int64_t e_end = e_begin + per_split < n_entries ? e_begin + per_split : n_entries;
-  const int64_t s0 = (int64_t)blockIdx.y * MV_SCHUNK + tid;
-  const C k = Gauss<C>::coef(width);
-  C off[MV_SC];
-  double acc[MV_SC];
-#pragma unroll
-  for (int q = 0; q < MV_SC; ++q) {
-    const int64_t s = s0 + (int64_t)q * MV_THREADS;
-    off[q] = s < S ? (C)offsets[s] : (C)0;
-    acc[q] = 0.0;
-  }
-  for (int64_t e0 = e_begin; e0 < e_end; e0 += MV_PL) {
-    const int ne = (int)(e_end - e0 < MV_PL ? e_end - e0 : MV_PL);
-    __syncthreads();
-    for (int m = tid; m < ne; m += MV_THREADS) {
-      const int64_t e = e0 + m, t = e / P;
-      int64_t i, j;
-      pair_of(e - t * P, n, &i, &j);
-      const TX* xi = X + (t * n + i) * 3;
-      const TX* xj = X + (t * n + j) * 3;
-      const TF* fi = F + (t * n + i) * 3;
-      const TF* fj = F + (t * n + j) * 3;
-      C d0 = (C)xi[0] - (C)xj[0], d1 = (C)xi[1] - (C)xj[1], d2 = (C)xi[2] - (C)xj[2];
-      if (PBC) {
-        CellFrame<C> h;
-        mv_cell(box, bstride, t, h);
-        brick_image(d0, d1, d2, h);
-      }
-      sx[m] = sq_norm3(d0, d1, d2);
-      su[m] = d0 * ((C)fi[0] - (C)fj[0]) + d1 * ((C)fi[1] - (C)fj[1]) + d2 * ((C)fi[2] - (C)fj[2]);
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int m = 0; m < ne; ++m) {
-      const C x = sx[m], u = su[m];
-#pragma unroll
-      for (int q = 0; q < MV_SC; ++q) {
-        const C tt = x - off[q];
-        acc[q] += (double)(tt * Gauss<C>::g(tt, k) * u);
-      }
-    }
-  }
-  double* slab = slabs + (int64_t)blockIdx.x * S;
-#pragma unroll
-  for (int q = 0; q < MV_SC; ++q) {
-    const int64_t s = s0 + (int64_t)q * MV_THREADS;
-    if (s < S) slab[s] = acc[q];
-  }
-}
-
-// ---- S offsets, residual shift, per-site form.  Grid (K splits of the frames, offset chunks).
-// slabs[k][s][0] = sum F_i . G~_s,i, slabs[k][s][1] = sum |G~_s,i|^2 over split k's frames, G~ = G w^2 / 8.
-// PBC: d is wrapped inside the j loop, under the cell of frame f (workgroup-uniform; a `whole` stage holds several).
-template <typename TX, typename TF, bool PBC>
-__global__ __launch_bounds__(MV_THREADS) void gauss_shift_kernel(const TX* __restrict__ X, const TF* __restrict__ F,
-                                                                  int64_t T, int32_t n,
-                                                                  const double* __restrict__ offsets, int64_t S,
-                                                                  double width, int64_t frames_per_split,
-                                                                  double* __restrict__ slabs,
-                                                                  const TX* __restrict__ box, int32_t bstride) {
-  typedef typename Promote<TX, TF>::type C;
-  __shared__ C sx[MV_JT * 3];
-  const int tid = threadIdx.x;
-  const int64_t t_begin = (int64_t)blockIdx.x * frames_per_split;
-  const int64_t t_end = t_begin + frames_per_split < T ? t_begin + frames_per_split : T;
-  const int64_t s0 = (int64_t)blockIdx.y * MV_SCHUNK + tid;
-  const C k = Gauss<C>::coef(width);
-  C off[MV_SC];
-  double ip[MV_SC], gs[MV_SC];
-#pragma unroll
-  for (int q = 0; q < MV_SC; ++q) {
-    const int64_t s = s0 + (int64_t)q * MV_THREADS;
-    off[q] = s < S ? (C)offsets[s] : (C)0;
-    ip[q] = gs[q] = 0.0;
-  }
-  const bool whole = n <= MV_JT;      // whole frames in LDS, MV_JT / n of them per stage
-  const int fb = whole ? MV_JT / n : 1;
-  for (int64_t t0 = t_begin; t0 < t_end; t0 += fb) {
-    const int nf = (int)(t_end - t0 < fb ? t_end - t0 : fb);
-    if (whole) {
-      __syncthreads();
-      const TX* src = X + t0 * n * 3;
-      for (int m = tid; m < nf * n * 3; m += MV_THREADS) sx[m] = (C)src[m];
-      __syncthreads();
-    }
-    for (int f = 0; f < nf; ++f) {
-      const int64_t t = t0 + f;
-      CellFrame<C> h = {};
-      if (PBC) mv_cell(box, bstride, t, h);
-      for (int64_t i = 0; i < n; ++i) {
-        const TX* xi = X + (t * n + i) * 3;
-        const TF* fi = F + (t * n + i) * 3;
-        C r0, r1, r2;
-        if (whole) {
-          r0 = sx[(f * n + i) * 3];
-          r1 = sx[(f * n + i) * 3 + 1];
-          r2 = sx[(f * n + i) * 3 + 2];
-        } else {
-          r0 = (C)xi[0];
-          r1 = (C)xi[1];
-          r2 = (C)xi[2];
-        }
-        double g[MV_SC][3];
-#pragma unroll
-        for (int q = 0; q < MV_SC; ++q) g[q][0] = g[q][1] = g[q][2] = 0.0;
-        for (int64_t j0 = 0; j0 < n; j0 += MV_JT) {
-          const int jn = (int)(n - j0 < MV_JT ? n - j0 : MV_JT);
-          const C* base = sx + (whole ? f * n * 3 : 0);
-          if (!whole) {
-            __syncthreads();
-            const TX* src = X + (t * n + j0) * 3;
-            for (int m = tid; m < jn * 3; m += MV_THREADS) sx[m] = (C)src[m];
-            __syncthreads();
-          }
-          for (int j = 0; j < jn; ++j) {
-            C d0 = r0 - base[3 * j], d1 = r1 - base[3 * j + 1], d2 = r2 - base[3 * j + 2];
-            if (PBC) brick_image(d0, d1, d2, h);
-            const C x = sq_norm3(d0, d1, d2);
-            const double e0 = (double)d0, e1 = (double)d1, e2 = (double)d2;
-#pragma unroll
-            for (int q = 0; q < MV_SC; ++q) {
-              const C tt = x - off[q];
-              const double c = (double)(tt * Gauss<C>::g(tt, k));
-              g[q][0] += c * e0;
-              g[q][1] += c * e1;
-              g[q][2] += c * e2;
-            }
-          }
-        }
-        const double f0 = (double)fi[0], f1 = (double)fi[1], f2 = (double)fi[2];
-#pragma unroll
-        for (int q = 0; q < MV_SC; ++q) {
-          ip[q] += f0 * g[q][0] + f1 * g[q][1] + f2 * g[q][2];
-          gs[q] += g[q][0] * g[q][0] + g[q][1] * g[q][1] + g[q][2] * g[q][2];
-        }
-      }
-    }
-  }
-  double* slab = slabs + (int64_t)blockIdx.x * S * 2;
-#pragma unroll
-  for (int q = 0; q < MV_SC; ++q) {
-    const int64_t s = s0 + (int64_t)q * MV_THREADS;
-    if (s < S) {
-      slab[2 * s] = ip[q];
-      slab[2 * s + 1] = gs[q];
-    }
   }
 }
 
@@ -441,6 +223,14 @@ static int mv_box(const char* who, const void* box, int32_t box_stride) {
   return AGGF_OK;
 }
 
+// the cell of a `_cell` entry and its image selector: AGGF_IMAGES_BRICK (the form of box_stride 9) or AGGF_IMAGES_NEAREST
+static int mv_cell_arg(const char* who, const void* cell, int images) {
+  if (!cell) return fail(AGGF_ERR_ARG, "%s: NULL cell", who);
+  if (images != AGGF_IMAGES_BRICK && images != AGGF_IMAGES_NEAREST)
+    return fail(AGGF_ERR_ARG, "%s: images %d is neither AGGF_IMAGES_BRICK nor AGGF_IMAGES_NEAREST", who, images);
+  return AGGF_OK;
+}
+
 static bool mv_samples_ok(int64_t S) { return S > 0 && ceil_div(S, MV_SCHUNK) <= 65535; }
 
 static size_t proj_ws(int64_t T, int32_t n, int64_t S) {
@@ -464,10 +254,14 @@ extern "C" size_t aggf_gauss_pair_forces_workspace_bytes(int64_t T, int32_t n) {
 
 template <typename TX>
 static void launch_site(dim3 grid, hipStream_t stream, const void* X, int64_t T, int32_t n, const SitePlan& p,
-                        double offset, double width, void* G, double* eslab, const void* box, int32_t bstride) {
+                        double offset, double width, void* G, double* eslab, const void* box, int32_t bstride,
+                        bool near) {
   const TX k = Gauss<TX>::coef(width);
   const double scale = 8.0 / (width * width);
-  if (box)
+  if (box && near)
+    AGGF_LAUNCH((gauss_site_forces_kernel<TX, true, CELL_NEAR>), grid, dim3(MV_THREADS), 0, stream, (const TX*)X, T, n,
+                p.fpb, p.iblk, p.n_iblk, p.n_blocks, (TX)offset, k, scale, (TX*)G, eslab, (const TX*)box, bstride);
+  else if (box)
     AGGF_LAUNCH((gauss_site_forces_kernel<TX, true>), grid, dim3(MV_THREADS), 0, stream, (const TX*)X, T, n, p.fpb,
                 p.iblk, p.n_iblk, p.n_blocks, (TX)offset, k, scale, (TX*)G, eslab, (const TX*)box, bstride);
   else
@@ -475,39 +269,55 @@ static void launch_site(dim3 grid, hipStream_t stream, const void* X, int64_t T,
                 p.iblk, p.n_iblk, p.n_blocks, (TX)offset, k, scale, (TX*)G, eslab, (const TX*)nullptr, 0);
 }
 
-extern "C" int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
-                                      const void* box, int32_t box_stride, void* G, void* E, void* ws, size_t ws_bytes,
-                                      void* stream_v) {
+static int gauss_pair_forces(const char* who, const void* X, int64_t T, int32_t n, int dtype, double offset,
+                            double width, const void* box, int32_t box_stride, bool near, void* G, void* E, void* ws,
+                            size_t ws_bytes, void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
-  if (!X || (!G && !E)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: NULL pointer");
-  if (!mv_dtype_ok(dtype)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: bad dtype");
-  if (!mv_shape_ok(T, n)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: bad shape (T=%lld, n=%d)", (long long)T, n);
-  if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: width must be positive");
-  const int rcb = mv_box("aggf_gauss_pair_forces", box, box_stride);
+  if (!X || (!G && !E)) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
+  if (!mv_dtype_ok(dtype)) return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
+  if (!mv_shape_ok(T, n)) return fail(AGGF_ERR_ARG, "%s: bad shape (T=%lld, n=%d)", who, (long long)T, n);
+  if (!(width > 0.0)) return fail(AGGF_ERR_ARG, "%s: width must be positive", who);
+  const int rcb = mv_box(who, box, box_stride);
   if (rcb != AGGF_OK) return rcb;
   const SitePlan p = site_plan(T, n);
   double* eslab = nullptr;
   if (E) {
-    if (!ws) return fail(AGGF_ERR_ARG, "aggf_gauss_pair_forces: NULL workspace");
+    if (!ws) return fail(AGGF_ERR_ARG, "%s: NULL workspace", who);
     if (ws_bytes < (size_t)(T * p.n_iblk) * sizeof(double))
-      return fail(AGGF_ERR_WORKSPACE, "aggf_gauss_pair_forces: workspace too small");
+      return fail(AGGF_ERR_WORKSPACE, "%s: workspace too small", who);
     eslab = (double*)ws;
   }
   const dim3 grid((unsigned)(p.n_blocks < MV_MAX_GRID ? p.n_blocks : MV_MAX_GRID));
   const int64_t fg = ceil_div(T, 256) < 4096 ? ceil_div(T, 256) : 4096;
   if (dtype == AGGF_F64) {
-    launch_site<double>(grid, stream, X, T, n, p, offset, width, G, eslab, box, box_stride);
+    launch_site<double>(grid, stream, X, T, n, p, offset, width, G, eslab, box, box_stride, near);
     AGGF_LAUNCH_OK();
     if (E) AGGF_LAUNCH(gauss_energy_finish_kernel<double>, dim3((unsigned)fg), dim3(256), 0, stream, eslab, T, p.n_iblk,
                        (double*)E);
   } else {
-    launch_site<float>(grid, stream, X, T, n, p, offset, width, G, eslab, box, box_stride);
+    launch_site<float>(grid, stream, X, T, n, p, offset, width, G, eslab, box, box_stride, near);
     AGGF_LAUNCH_OK();
     if (E) AGGF_LAUNCH(gauss_energy_finish_kernel<float>, dim3((unsigned)fg), dim3(256), 0, stream, eslab, T, p.n_iblk,
                        (float*)E);
   }
   AGGF_LAUNCH_OK();
   return AGGF_OK;
+}
+
+extern "C" int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
+                                      const void* box, int32_t box_stride, void* G, void* E, void* ws, size_t ws_bytes,
+                                      void* stream_v) {
+  return gauss_pair_forces("aggf_gauss_pair_forces", X, T, n, dtype, offset, width, box, box_stride, false, G, E, ws,
+                           ws_bytes, stream_v);
+}
+
+extern "C" int aggf_gauss_pair_forces_cell(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
+                                           const void* cell, void* G, void* E, void* ws, size_t ws_bytes,
+                                           void* stream_v, int images) {
+  const int rc = mv_cell_arg("aggf_gauss_pair_forces_cell", cell, images);
+  if (rc != AGGF_OK) return rc;
+  return gauss_pair_forces("aggf_gauss_pair_forces_cell", X, T, n, dtype, offset, width, cell, 9,
+                           images == AGGF_IMAGES_NEAREST, G, E, ws, ws_bytes, stream_v);
 }
 
 extern "C" size_t aggf_gauss_proj_workspace_bytes(int64_t T, int32_t n, int64_t S) {
@@ -520,17 +330,24 @@ extern "C" size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t
   return shift_ws(T, S);
 }
 
-// (box NULL: the open instantiation)
+// (box NULL: the open instantiation; near: the nearest-image one)
 #define AGGF_MV_LAUNCH(KERNEL, TF, PBC, BOX, STRIDE)                                                               \
   AGGF_LAUNCH((KERNEL<TX, TF, PBC>), grid, dim3(MV_THREADS), 0, stream, X, (const TF*)F, T, n, offsets, S, width,  \
               p.per_split, slabs, BOX, STRIDE)
+#define AGGF_MV_LAUNCH_NEAR(KERNEL, TF)                                                                            \
+  AGGF_LAUNCH((KERNEL<TX, TF, true, CELL_NEAR>), grid, dim3(MV_THREADS), 0, stream, X, (const TF*)F, T, n, offsets, \
+              S, width, p.per_split, slabs, (const TX*)box, bstride)
 #define AGGF_MV_LAUNCH_X(NAME, KERNEL)                                                                             \
   template <typename TX>                                                                                           \
   static void NAME(const TX* X, const void* F, int f_dtype, int64_t T, int32_t n, const double* offsets, int64_t S, \
-                   double width, const SplitPlan& p, double* slabs, const void* box, int32_t bstride,              \
+                   double width, const SplitPlan& p, double* slabs, const void* box, int32_t bstride, bool near,   \
                    hipStream_t stream) {                                                                           \
     const dim3 grid((unsigned)p.K, (unsigned)p.n_sch);                                                             \
-    if (box && f_dtype == AGGF_F64)                                                                                \
+    if (box && near && f_dtype == AGGF_F64)                                                                        \
+      AGGF_MV_LAUNCH_NEAR(KERNEL, double);                                                                         \
+    else if (box && near)                                                                                          \
+      AGGF_MV_LAUNCH_NEAR(KERNEL, float);                                                                          \
+    else if (box && f_dtype == AGGF_F64)                                                                           \
       AGGF_MV_LAUNCH(KERNEL, double, true, (const TX*)box, bstride);                                               \
     else if (box)                                                                                                  \
       AGGF_MV_LAUNCH(KERNEL, float, true, (const TX*)box, bstride);                                                \
@@ -542,6 +359,7 @@ extern "C" size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t
 AGGF_MV_LAUNCH_X(launch_proj_x, gauss_proj_kernel)
 AGGF_MV_LAUNCH_X(launch_shift_x, gauss_shift_kernel)
 #undef AGGF_MV_LAUNCH_X
+#undef AGGF_MV_LAUNCH_NEAR
 #undef AGGF_MV_LAUNCH
 
 static int mv_check(const char* who, const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
@@ -556,20 +374,20 @@ static int mv_check(const char* who, const void* X, int x_dtype, const void* F, 
   return mv_box(who, box, box_stride);
 }
 
-extern "C" int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
-                               const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
-                               double* out, void* ws, size_t ws_bytes, void* stream_v) {
+static int gauss_proj(const char* who, const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                      const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                      bool near, double* out, void* ws, size_t ws_bytes, void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   const size_t need = mv_shape_ok(T, n) && mv_samples_ok(S) ? proj_ws(T, n, S) : 256;
-  const int rc = mv_check("aggf_gauss_proj", X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, out, out,
+  const int rc = mv_check(who, X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, out, out,
                           ws, ws_bytes, need);
   if (rc != AGGF_OK) return rc;
   const SplitPlan p = split_plan(T * ((int64_t)n * (n - 1) / 2), MV_PL, S, 1);
   double* slabs = (double*)ws;
   if (x_dtype == AGGF_F64)
-    launch_proj_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
+    launch_proj_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, near, stream);
   else
-    launch_proj_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
+    launch_proj_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, near, stream);
   AGGF_LAUNCH_OK();
   const int64_t g = ceil_div(S, 256) < 1024 ? ceil_div(S, 256) : 1024;
   AGGF_LAUNCH(mapval_slab_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, slabs, p.K, S, 1,
@@ -578,20 +396,20 @@ extern "C" int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_
   return AGGF_OK;
 }
 
-extern "C" int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
-                                const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
-                                double* ip, double* gsq, void* ws, size_t ws_bytes, void* stream_v) {
+static int gauss_shift(const char* who, const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                      const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                      bool near, double* ip, double* gsq, void* ws, size_t ws_bytes, void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   const size_t need = mv_shape_ok(T, n) && mv_samples_ok(S) ? shift_ws(T, S) : 256;
-  const int rc = mv_check("aggf_gauss_shift", X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, ip, gsq,
+  const int rc = mv_check(who, X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, ip, gsq,
                           ws, ws_bytes, need);
   if (rc != AGGF_OK) return rc;
   const SplitPlan p = split_plan(T, 1, S, 2);
   double* slabs = (double*)ws;
   if (x_dtype == AGGF_F64)
-    launch_shift_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
+    launch_shift_x((const double*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, near, stream);
   else
-    launch_shift_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, stream);
+    launch_shift_x((const float*)X, F, f_dtype, T, n, offsets, S, width, p, slabs, box, box_stride, near, stream);
   AGGF_LAUNCH_OK();
   const double sc = 8.0 / (width * width);
   const int64_t g = ceil_div(S, 256) < 1024 ? ceil_div(S, 256) : 1024;
@@ -599,6 +417,38 @@ extern "C" int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f
               gsq);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
+}
+
+extern "C" int aggf_gauss_proj(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                               const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                               double* out, void* ws, size_t ws_bytes, void* stream_v) {
+  return gauss_proj("aggf_gauss_proj", X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, false, out, ws,
+                    ws_bytes, stream_v);
+}
+
+extern "C" int aggf_gauss_proj_cell(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                                    const double* offsets, int64_t S, double width, const void* cell, double* out,
+                                    void* ws, size_t ws_bytes, void* stream_v, int images) {
+  const int rc = mv_cell_arg("aggf_gauss_proj_cell", cell, images);
+  if (rc != AGGF_OK) return rc;
+  return gauss_proj("aggf_gauss_proj_cell", X, x_dtype, F, f_dtype, T, n, offsets, S, width, cell, 9,
+                    images == AGGF_IMAGES_NEAREST, out, ws, ws_bytes, stream_v);
+}
+
+extern "C" int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                                const double* offsets, int64_t S, double width, const void* box, int32_t box_stride,
+                                double* ip, double* gsq, void* ws, size_t ws_bytes, void* stream_v) {
+  return gauss_shift("aggf_gauss_shift", X, x_dtype, F, f_dtype, T, n, offsets, S, width, box, box_stride, false, ip,
+                     gsq, ws, ws_bytes, stream_v);
+}
+
+extern "C" int aggf_gauss_shift_cell(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                                     const double* offsets, int64_t S, double width, const void* cell, double* ip,
+                                     double* gsq, void* ws, size_t ws_bytes, void* stream_v, int images) {
+  const int rc = mv_cell_arg("aggf_gauss_shift_cell", cell, images);
+  if (rc != AGGF_OK) return rc;
+  return gauss_shift("aggf_gauss_shift_cell", X, x_dtype, F, f_dtype, T, n, offsets, S, width, cell, 9,
+                     images == AGGF_IMAGES_NEAREST, ip, gsq, ws, ws_bytes, stream_v);
 }
 
 extern "C" size_t aggf_dot_workspace_bytes(void) { return MV_DOT_BLOCKS * sizeof(double); }

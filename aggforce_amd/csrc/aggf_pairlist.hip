@@ -70,9 +70,9 @@ __device__ __forceinline__ void pairlist_body(const T* __restrict__ X, const T* 
         if (bstride != 0) box_lengths(box + t * bstride, L, iL);
         d0 = min_image(d0, L[0], iL[0]), d1 = min_image(d1, L[1], iL[1]), d2 = min_image(d2, L[2], iL[2]);
       }
-      if (CELL == CELL_TRI) {
+      if (CELL == CELL_TRI || CELL == CELL_NEAR) {
         cell_frame(box + t * 9, h);
-        brick_image(d0, d1, d2, h);
+        cell_image<CELL>(d0, d1, d2, h);
       }
       T e0 = 0, e1 = 0, e2 = 0;
       if (MODE == AGGF_PAIR_DOT) {
@@ -102,15 +102,16 @@ __global__ __launch_bounds__(256) void pairlist_pbc_kernel(const T* __restrict__
   pairlist_body<T, MODE, CELL_BOX>(X, C, V, Y, pairs, nT, m, n, P, frames, box, bstride, out);
 }
 
-// The triclinic form, an overload with a third template argument (CELL_TRI, the only value instantiated): cell is
-// (T, 9), a row-major 3 x 3 cell per frame (brick_image, aggf_common.h).  pairlist_pbc_kernel<T, MODE> is the box form.
+// The triclinic forms, an overload with a third template argument: cell is (T, 9), a row-major 3 x 3 cell per frame, and
+// u its brick image (CELL_TRI) or its nearest image (CELL_NEAR; brick_image, nearest_image: aggf_common.h).
+// pairlist_pbc_kernel<T, MODE> is the box form.
 template <typename T, int MODE, int CELL>
 __global__ __launch_bounds__(256) void pairlist_pbc_kernel(const T* __restrict__ X, const T* __restrict__ C,
                                                            const T* __restrict__ V, const T* __restrict__ Y,
                                                            const int32_t* __restrict__ pairs, int64_t nT, int32_t m,
                                                            int32_t n, int64_t P, int64_t frames,
                                                            const T* __restrict__ cell, T* __restrict__ out) {
-  static_assert(CELL == CELL_TRI, "the triclinic form");
+  static_assert(CELL == CELL_TRI || CELL == CELL_NEAR, "a triclinic form");
   pairlist_body<T, MODE, CELL>(X, C, V, Y, pairs, nT, m, n, P, frames, cell, 9, out);
 }
 
@@ -168,8 +169,8 @@ __device__ __forceinline__ void pairlist_pull_body(const TI* __restrict__ W, con
     TI L[3] = {0, 0, 0}, iL[3] = {0, 0, 0};
     CellFrame<TI> h = {};
     const bool box_ok = CELL == CELL_BOX   ? box_lengths(box + t * bstride, L, iL)
-                        : CELL == CELL_TRI ? cell_frame(box + t * 9, h)
-                                           : true;
+                        : CELL == CELL_TRI || CELL == CELL_NEAR ? cell_frame(box + t * 9, h)
+                                                                : true;
     const double zero = box_ok ? 0.0 : __builtin_nan("");
     double a0 = zero, a1 = zero, a2 = zero;
     for (int64_t e = FORM == PLP_LANE ? beg : beg + lane; e < end; e += FORM == PLP_LANE ? 1 : 64) {
@@ -181,7 +182,7 @@ __device__ __forceinline__ void pairlist_pull_body(const TI* __restrict__ W, con
       const TI* r = oth + 3 * (int64_t)o;
       TI u0 = o0 - r[0], u1 = o1 - r[1], u2 = o2 - r[2];
       if (CELL == CELL_BOX) u0 = min_image(u0, L[0], iL[0]), u1 = min_image(u1, L[1], iL[1]), u2 = min_image(u2, L[2], iL[2]);
-      if (CELL == CELL_TRI) brick_image(u0, u1, u2, h);
+      if (CELL == CELL_TRI || CELL == CELL_NEAR) cell_image<CELL>(u0, u1, u2, h);
       a0 += (double)(wv * u0), a1 += (double)(wv * u1), a2 += (double)(wv * u2);
     }
     if (FORM == PLP_WAVE) {
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256) void pairlist_pull_pbc_kernel(const TI* __rest
   pairlist_pull_body<TI, TO, HAS_DV, FORM, CELL_BOX>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box, bstride, out);
 }
 
-// (the triclinic form: an overload with a fifth template argument, as pairlist_pbc_kernel's)
+// (the triclinic forms: an overload with a fifth template argument, as pairlist_pbc_kernel's)
 template <typename TI, typename TO, bool HAS_DV, int FORM, int CELL>
 __global__ __launch_bounds__(256) void pairlist_pull_pbc_kernel(const TI* __restrict__ W, const TI* __restrict__ Dv,
                                                                 const TI* __restrict__ Own, const TI* __restrict__ Oth,
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(256) void pairlist_pull_pbc_kernel(const TI* __rest
                                                                 const int32_t* __restrict__ idx, int64_t nT, int32_t ns,
                                                                 int32_t no, int64_t P, const TI* __restrict__ cell,
                                                                 TO* __restrict__ out) {
-  static_assert(CELL == CELL_TRI, "the triclinic form");
+  static_assert(CELL == CELL_TRI || CELL == CELL_NEAR, "a triclinic form");
   pairlist_pull_body<TI, TO, HAS_DV, FORM, CELL>(W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, cell, 9, out);
 }
 
@@ -249,23 +250,29 @@ static int pairlist_shape(const char* who, int64_t T, int32_t m, int32_t n, int6
   return AGGF_OK;
 }
 
-// (box NULL: the open kernels, with the arguments they have always had)
+// (box NULL: the open kernels, with the arguments they have always had; near: the nearest-image form of a (T, 9) cell)
 template <typename T>
 static void launch_pairlist(int mode, dim3 grid, hipStream_t stream, const void* X, const void* C, const void* V,
                             const void* Y, const int32_t* pairs, int64_t nT, int32_t m, int32_t n, int64_t P,
-                            int64_t frames, const void* box, int32_t bstride, void* out) {
+                            int64_t frames, const void* box, int32_t bstride, bool near, void* out) {
   const dim3 block(256);
-  if (box && bstride == 9) {
-#define AGGF_PL_CELL(MODE)                                                                                      \
-  AGGF_LAUNCH((pairlist_pbc_kernel<T, MODE, CELL_TRI>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,   \
+#define AGGF_PL_CELL(MODE, CELL)                                                                                \
+  AGGF_LAUNCH((pairlist_pbc_kernel<T, MODE, CELL>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,   \
               (const T*)Y, pairs, nT, m, n, P, frames, (const T*)box, (T*)out)
+  if (box && bstride == 9 && near) {
     if (mode == AGGF_PAIR_DIST)
-      AGGF_PL_CELL(AGGF_PAIR_DIST);
+      AGGF_PL_CELL(AGGF_PAIR_DIST, CELL_NEAR);
     else if (mode == AGGF_PAIR_SQDIST)
-      AGGF_PL_CELL(AGGF_PAIR_SQDIST);
+      AGGF_PL_CELL(AGGF_PAIR_SQDIST, CELL_NEAR);
     else
-      AGGF_PL_CELL(AGGF_PAIR_DOT);
-#undef AGGF_PL_CELL
+      AGGF_PL_CELL(AGGF_PAIR_DOT, CELL_NEAR);
+  } else if (box && bstride == 9) {
+    if (mode == AGGF_PAIR_DIST)
+      AGGF_PL_CELL(AGGF_PAIR_DIST, CELL_TRI);
+    else if (mode == AGGF_PAIR_SQDIST)
+      AGGF_PL_CELL(AGGF_PAIR_SQDIST, CELL_TRI);
+    else
+      AGGF_PL_CELL(AGGF_PAIR_DOT, CELL_TRI);
   } else if (box) {
 #define AGGF_PL_PBC(MODE)                                                                                       \
   AGGF_LAUNCH((pairlist_pbc_kernel<T, MODE>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,    \
@@ -286,16 +293,25 @@ static void launch_pairlist(int mode, dim3 grid, hipStream_t stream, const void*
   else
     AGGF_LAUNCH((pairlist_kernel<T, AGGF_PAIR_DOT>), grid, block, 0, stream, (const T*)X, (const T*)C, (const T*)V,
                 (const T*)Y, pairs, nT, m, n, P, frames, (T*)out);
+#undef AGGF_PL_CELL
 }
 
 template <typename TI, typename TO, bool HAS_DV>
 static void launch_pull_form(int form, hipStream_t stream, const void* W, const void* Dv, const void* Own,
                              const void* Oth, const int32_t* pairs, int32_t ocol, const int32_t* ptr,
                              const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, const void* box,
-                             int32_t bstride, void* out) {
+                             int32_t bstride, bool near, void* out) {
   const dim3 block(256);
   const int64_t tasks = nT * ns;
-  if (box && bstride == 9 && form == PLP_LANE)
+  if (box && bstride == 9 && near && form == PLP_LANE)
+    AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_LANE, CELL_NEAR>), pairlist_grid(ceil_div(tasks, 256)), block, 0,
+                stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
+                P, (const TI*)box, (TO*)out);
+  else if (box && bstride == 9 && near)
+    AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_WAVE, CELL_NEAR>), pairlist_grid(ceil_div(tasks, 4)), block, 0,
+                stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
+                P, (const TI*)box, (TO*)out);
+  else if (box && bstride == 9 && form == PLP_LANE)
     AGGF_LAUNCH((pairlist_pull_pbc_kernel<TI, TO, HAS_DV, PLP_LANE, CELL_TRI>), pairlist_grid(ceil_div(tasks, 256)), block, 0,
                 stream, (const TI*)W, (const TI*)Dv, (const TI*)Own, (const TI*)Oth, pairs, ocol, ptr, idx, nT, ns, no,
                 P, (const TI*)box, (TO*)out);
@@ -325,14 +341,14 @@ static void launch_pull_form(int form, hipStream_t stream, const void* W, const 
 static void launch_pull(int in_dtype, int out_dtype, int32_t max_deg, hipStream_t stream, const void* W, const void* Dv,
                         const void* Own, const void* Oth, const int32_t* pairs, int32_t ocol, const int32_t* ptr,
                         const int32_t* idx, int64_t nT, int32_t ns, int32_t no, int64_t P, const void* box,
-                        int32_t bstride, void* out) {
+                        int32_t bstride, bool near, void* out) {
   if (ns == 0) return;
   const int form = max_deg > PLP_LANE_DEG ? PLP_WAVE : PLP_LANE;
 #define AGGF_PULL_FORM(TI, TO)                                                                                       \
   (Dv ? launch_pull_form<TI, TO, true>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box,     \
-                                       bstride, out)                                                                 \
+                                       bstride, near, out)                                                           \
       : launch_pull_form<TI, TO, false>(form, stream, W, Dv, Own, Oth, pairs, ocol, ptr, idx, nT, ns, no, P, box,    \
-                                        bstride, out))
+                                        bstride, near, out))
   if (in_dtype == AGGF_F32)
     AGGF_PULL_FORM(float, float);
   else if (out_dtype == AGGF_F32)
@@ -353,7 +369,7 @@ static int pairlist_box(const char* who, const void* box, int32_t box_stride) {
 // K9c, open (box NULL) or under a box: one launch plan for both
 static int pair_list_dist(const char* who, const void* X, const void* C, const void* V, const void* Y,
                           const int32_t* pairs, int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode,
-                          const void* box, int32_t box_stride, void* out, hipStream_t stream) {
+                          const void* box, int32_t box_stride, bool near, void* out, hipStream_t stream) {
   int64_t count = 0;
   const int rc = pairlist_shape(who, T, m, n, P, &count);
   if (rc != AGGF_OK) return rc;
@@ -370,9 +386,9 @@ static int pair_list_dist(const char* who, const void* X, const void* C, const v
   const int64_t waves = pblocks * ceil_div(T, frames);  // <= count
   const dim3 grid = pairlist_grid(ceil_div(waves, 4));
   if (dtype == AGGF_F64)
-    launch_pairlist<double>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, box, box_stride, out);
+    launch_pairlist<double>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, box, box_stride, near, out);
   else
-    launch_pairlist<float>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, box, box_stride, out);
+    launch_pairlist<float>(mode, grid, stream, X, C, V, Y, pairs, T, m, n, P, frames, box, box_stride, near, out);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
 }
@@ -381,8 +397,8 @@ static int pair_list_dist(const char* who, const void* X, const void* C, const v
 static int pair_list_pull(const char* who, const void* W, const void* Dv, const void* X, const void* C,
                           const int32_t* pairs, const int32_t* a_ptr, const int32_t* a_idx, const int32_t* b_ptr,
                           const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m, int32_t n,
-                          int64_t P, int in_dtype, const void* box, int32_t box_stride, void* A, void* B, int out_dtype,
-                          hipStream_t stream) {
+                          int64_t P, int in_dtype, const void* box, int32_t box_stride, bool near, void* A, void* B,
+                          int out_dtype, hipStream_t stream) {
   int64_t count = 0;
   const int rc = pairlist_shape(who, T, m, n, P, &count);
   if (rc != AGGF_OK) return rc;
@@ -397,10 +413,10 @@ static int pair_list_pull(const char* who, const void* W, const void* Dv, const 
     return fail(AGGF_ERR_ARG, "%s: an output without its incidence table", who);
   if (A)
     launch_pull(in_dtype, out_dtype, max_deg_a, stream, W, Dv, X, C, pairs, 0, a_ptr, a_idx, T, n, m, P, box,
-                box_stride, A);
+                box_stride, near, A);
   if (B)
     launch_pull(in_dtype, out_dtype, max_deg_b, stream, W, Dv, C, X, pairs, 1, b_ptr, b_idx, T, m, n, P, box,
-                box_stride, B);
+                box_stride, near, B);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
 }
@@ -412,7 +428,7 @@ using namespace aggf;
 extern "C" int aggf_pair_list_dist(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
                                    int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, void* out,
                                    void* stream_v) {
-  return pair_list_dist("aggf_pair_list_dist", X, C, V, Y, pairs, T, m, n, P, dtype, mode, nullptr, 0, out,
+  return pair_list_dist("aggf_pair_list_dist", X, C, V, Y, pairs, T, m, n, P, dtype, mode, nullptr, 0, false, out,
                         (hipStream_t)stream_v);
 }
 
@@ -421,8 +437,25 @@ extern "C" int aggf_pair_list_dist_pbc(const void* X, const void* C, const void*
                                        int mode, const void* box, int32_t box_stride, void* out, void* stream_v) {
   const int rc = pairlist_box("aggf_pair_list_dist_pbc", box, box_stride);
   if (rc != AGGF_OK) return rc;
-  return pair_list_dist("aggf_pair_list_dist_pbc", X, C, V, Y, pairs, T, m, n, P, dtype, mode, box, box_stride, out,
-                        (hipStream_t)stream_v);
+  return pair_list_dist("aggf_pair_list_dist_pbc", X, C, V, Y, pairs, T, m, n, P, dtype, mode, box, box_stride, false,
+                        out, (hipStream_t)stream_v);
+}
+
+// the cell of a `_cell` entry and its image selector: AGGF_IMAGES_BRICK (the form of box_stride 9) or AGGF_IMAGES_NEAREST
+static int pairlist_cell(const char* who, const void* cell, int images) {
+  if (!cell) return fail(AGGF_ERR_ARG, "%s: NULL cell", who);
+  if (images != AGGF_IMAGES_BRICK && images != AGGF_IMAGES_NEAREST)
+    return fail(AGGF_ERR_ARG, "%s: images %d is neither AGGF_IMAGES_BRICK nor AGGF_IMAGES_NEAREST", who, images);
+  return AGGF_OK;
+}
+
+extern "C" int aggf_pair_list_dist_cell(const void* X, const void* C, const void* V, const void* Y,
+                                        const int32_t* pairs, int64_t T, int32_t m, int32_t n, int64_t P, int dtype,
+                                        int mode, const void* cell, void* out, void* stream_v, int images) {
+  const int rc = pairlist_cell("aggf_pair_list_dist_cell", cell, images);
+  if (rc != AGGF_OK) return rc;
+  return pair_list_dist("aggf_pair_list_dist_cell", X, C, V, Y, pairs, T, m, n, P, dtype, mode, cell, 9,
+                        images == AGGF_IMAGES_NEAREST, out, (hipStream_t)stream_v);
 }
 
 extern "C" int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void* C, const int32_t* pairs,
@@ -431,7 +464,7 @@ extern "C" int aggf_pair_list_pull(const void* W, const void* Dv, const void* X,
                                    int32_t n, int64_t P, int in_dtype, void* A, void* B, int out_dtype,
                                    void* stream_v) {
   return pair_list_pull("aggf_pair_list_pull", W, Dv, X, C, pairs, a_ptr, a_idx, b_ptr, b_idx, max_deg_a, max_deg_b, T,
-                        m, n, P, in_dtype, nullptr, 0, A, B, out_dtype, (hipStream_t)stream_v);
+                        m, n, P, in_dtype, nullptr, 0, false, A, B, out_dtype, (hipStream_t)stream_v);
 }
 
 extern "C" int aggf_pair_list_pull_pbc(const void* W, const void* Dv, const void* X, const void* C,
@@ -443,5 +476,19 @@ extern "C" int aggf_pair_list_pull_pbc(const void* W, const void* Dv, const void
   const int rc = pairlist_box("aggf_pair_list_pull_pbc", box, box_stride);
   if (rc != AGGF_OK) return rc;
   return pair_list_pull("aggf_pair_list_pull_pbc", W, Dv, X, C, pairs, a_ptr, a_idx, b_ptr, b_idx, max_deg_a,
-                        max_deg_b, T, m, n, P, in_dtype, box, box_stride, A, B, out_dtype, (hipStream_t)stream_v);
+                        max_deg_b, T, m, n, P, in_dtype, box, box_stride, false, A, B, out_dtype,
+                        (hipStream_t)stream_v);
+}
+
+extern "C" int aggf_pair_list_pull_cell(const void* W, const void* Dv, const void* X, const void* C,
+                                        const int32_t* pairs, const int32_t* a_ptr, const int32_t* a_idx,
+                                        const int32_t* b_ptr, const int32_t* b_idx, int32_t max_deg_a,
+                                        int32_t max_deg_b, int64_t T, int32_t m, int32_t n, int64_t P, int in_dtype,
+                                        const void* cell, void* A, void* B, int out_dtype, void* stream_v,
+                                        int images) {
+  const int rc = pairlist_cell("aggf_pair_list_pull_cell", cell, images);
+  if (rc != AGGF_OK) return rc;
+  return pair_list_pull("aggf_pair_list_pull_cell", W, Dv, X, C, pairs, a_ptr, a_idx, b_ptr, b_idx, max_deg_a,
+                        max_deg_b, T, m, n, P, in_dtype, cell, 9, images == AGGF_IMAGES_NEAREST, A, B, out_dtype,
+                        (hipStream_t)stream_v);
 }

@@ -48,8 +48,8 @@ static PairMinPlan pairmin_plan(int64_t T, int32_t m, int32_t n, int dtype) {
 }
 
 // dst: out when the plan has one split (root: the sqrt is applied here), else the (splits, m, n) partials
-// (one body for the three forms: CELL_OPEN, CELL_BOX -- min_image --, CELL_TRI -- box is (T, 9), a triclinic cell per
-// frame, brick_image)
+// (one body for the four forms: CELL_OPEN, CELL_BOX -- min_image --, CELL_TRI -- box is (T, 9), a triclinic cell per
+// frame, brick_image -- and CELL_NEAR -- the same cell, nearest_image)
 template <typename T, int CELL>
 __device__ __forceinline__ void pairmin_body(const T* __restrict__ X, const T* __restrict__ C, int64_t nT, int32_t m,
                                              int32_t n, int64_t jblocks, int64_t iblocks, int64_t frames,
@@ -77,13 +77,13 @@ __device__ __forceinline__ void pairmin_body(const T* __restrict__ X, const T* _
   for (int64_t t = t0; t < t1; ++t, x += xs, c += cs) {
     const T x0 = x[0], x1 = x[1], x2 = x[2];
     if (CELL == CELL_BOX && bstride != 0) box_lengths(box + t * bstride, L, iL);
-    if (CELL == CELL_TRI) cell_frame(box + t * 9, h);
+    if (CELL == CELL_TRI || CELL == CELL_NEAR) cell_frame(box + t * 9, h);
 #pragma unroll
     for (int r = 0; r < PM_ROWS; ++r) {
       const T* cr = c + coff[r];
       T d0 = x0 - cr[0], d1 = x1 - cr[1], d2 = x2 - cr[2];
       if (CELL == CELL_BOX) d0 = min_image(d0, L[0], iL[0]), d1 = min_image(d1, L[1], iL[1]), d2 = min_image(d2, L[2], iL[2]);
-      if (CELL == CELL_TRI) brick_image(d0, d1, d2, h);
+      if (CELL == CELL_TRI || CELL == CELL_NEAR) cell_image<CELL>(d0, d1, d2, h);
       acc[r] = nan_min(acc[r], pair_element<T, AGGF_PAIR_SQDIST>(d0, d1, d2, (T)0, (T)0, (T)0));
     }
   }
@@ -102,13 +102,13 @@ __global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, c
   pairmin_body<T, PBC ? CELL_BOX : CELL_OPEN>(X, C, nT, m, n, jblocks, iblocks, frames, box, bstride, root, dst);
 }
 
-// (the triclinic form: an overload with a third template argument, CELL_TRI the only value instantiated)
+// (the triclinic forms: an overload with a third template argument, CELL_TRI or CELL_NEAR)
 template <typename T, bool PBC, int CELL>
 __global__ __launch_bounds__(256) void pairmin_kernel(const T* __restrict__ X, const T* __restrict__ C, int64_t nT,
                                                       int32_t m, int32_t n, int64_t jblocks, int64_t iblocks,
                                                       int64_t frames, const T* __restrict__ cell, int root,
                                                       T* __restrict__ dst) {
-  static_assert(PBC && CELL == CELL_TRI, "the triclinic form");
+  static_assert(PBC && (CELL == CELL_TRI || CELL == CELL_NEAR), "a triclinic form");
   pairmin_body<T, CELL>(X, C, nT, m, n, jblocks, iblocks, frames, cell, 9, root, dst);
 }
 
@@ -131,12 +131,16 @@ static int64_t pairmin_ws_elems(const PairMinPlan& p, int32_t m, int32_t n) {
 
 template <typename T>
 static void launch_pairmin(const PairMinPlan& p, hipStream_t stream, const void* X, const void* C, int64_t nT,
-                           int32_t m, int32_t n, const void* box, int32_t bstride, int square, void* out, void* ws) {
+                           int32_t m, int32_t n, const void* box, int32_t bstride, bool near, int square, void* out,
+                           void* ws) {
   const dim3 grid((unsigned)(p.jblocks * p.iblocks * p.splits)), block(256);
   const bool split = p.splits > 1;
   const int root = !split && !square;
   T* dst = (T*)(split ? ws : out);
-  if (box && bstride == 9)
+  if (box && bstride == 9 && near)
+    AGGF_LAUNCH((pairmin_kernel<T, true, CELL_NEAR>), grid, block, 0, stream, (const T*)X, (const T*)C, nT, m, n, p.jblocks,
+                p.iblocks, p.frames, (const T*)box, root, dst);
+  else if (box && bstride == 9)
     AGGF_LAUNCH((pairmin_kernel<T, true, CELL_TRI>), grid, block, 0, stream, (const T*)X, (const T*)C, nT, m, n, p.jblocks,
                 p.iblocks, p.frames, (const T*)box, root, dst);
   else if (box)
@@ -165,32 +169,48 @@ extern "C" size_t aggf_pair_min_workspace_bytes(int64_t T, int32_t m, int32_t n,
   return (size_t)pairmin_ws_elems(p, m, n) * (dtype == AGGF_F64 ? 8 : 4);
 }
 
-extern "C" int aggf_pair_min(const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype, const void* box,
-                             int32_t box_stride, int square, void* out, void* ws, size_t ws_bytes, void* stream_v) {
+static int pair_min(const char* who, const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype,
+                    const void* box, int32_t box_stride, bool near, int square, void* out, void* ws, size_t ws_bytes,
+                    void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
-  if (T < 0 || m < 0 || n < 0) return fail(AGGF_ERR_ARG, "aggf_pair_min: negative shape");
-  if (dtype != AGGF_F32 && dtype != AGGF_F64) return fail(AGGF_ERR_ARG, "aggf_pair_min: bad dtype");
+  if (T < 0 || m < 0 || n < 0) return fail(AGGF_ERR_ARG, "%s: negative shape", who);
+  if (dtype != AGGF_F32 && dtype != AGGF_F64) return fail(AGGF_ERR_ARG, "%s: bad dtype", who);
   if (box_stride != 0 && box_stride != 3 && box_stride != 9)
-    return fail(AGGF_ERR_ARG, "aggf_pair_min: box_stride %d is none of 0, 3 and 9", box_stride);
-  if (box_stride == 9 && !box) return fail(AGGF_ERR_ARG, "aggf_pair_min: box_stride 9 without a cell");
+    return fail(AGGF_ERR_ARG, "%s: box_stride %d is none of 0, 3 and 9", who, box_stride);
+  if (box_stride == 9 && !box) return fail(AGGF_ERR_ARG, "%s: box_stride 9 without a cell", who);
   if (T == 0 || m == 0 || n == 0) return AGGF_OK;
   int64_t sites = 0;
   if (__builtin_mul_overflow(T, 3 * (int64_t)(m > n ? m : n), &sites) || sites > INT64_MAX / 8)
-    return fail(AGGF_ERR_ARG, "aggf_pair_min: T n does not fit a 64-bit byte offset");
-  if (!X || !C || !out) return fail(AGGF_ERR_ARG, "aggf_pair_min: NULL pointer");
+    return fail(AGGF_ERR_ARG, "%s: T n does not fit a 64-bit byte offset", who);
+  if (!X || !C || !out) return fail(AGGF_ERR_ARG, "%s: NULL pointer", who);
   const PairMinPlan p = pairmin_plan(T, m, n, dtype);
   const int64_t elems = pairmin_ws_elems(p, m, n);
-  if (elems == 0) return fail(AGGF_ERR_ARG, "aggf_pair_min: m n does not fit a 64-bit byte offset");
-  if (p.jblocks * p.iblocks * p.splits > 0x7fffffff) return fail(AGGF_ERR_ARG, "aggf_pair_min: too many output tiles");
+  if (elems == 0) return fail(AGGF_ERR_ARG, "%s: m n does not fit a 64-bit byte offset", who);
+  if (p.jblocks * p.iblocks * p.splits > 0x7fffffff) return fail(AGGF_ERR_ARG, "%s: too many output tiles", who);
   if (p.splits > 1) {
     const size_t esz = dtype == AGGF_F64 ? 8 : 4;
-    if (!ws || ws_bytes < (size_t)elems * esz) return fail(AGGF_ERR_WORKSPACE, "aggf_pair_min: workspace too small");
-    if ((uintptr_t)ws % esz) return fail(AGGF_ERR_WORKSPACE, "aggf_pair_min: workspace is not element-aligned");
+    if (!ws || ws_bytes < (size_t)elems * esz) return fail(AGGF_ERR_WORKSPACE, "%s: workspace too small", who);
+    if ((uintptr_t)ws % esz) return fail(AGGF_ERR_WORKSPACE, "%s: workspace is not element-aligned", who);
   }
   if (dtype == AGGF_F64)
-    launch_pairmin<double>(p, stream, X, C, T, m, n, box, box_stride, square, out, ws);
+    launch_pairmin<double>(p, stream, X, C, T, m, n, box, box_stride, near, square, out, ws);
   else
-    launch_pairmin<float>(p, stream, X, C, T, m, n, box, box_stride, square, out, ws);
+    launch_pairmin<float>(p, stream, X, C, T, m, n, box, box_stride, near, square, out, ws);
   AGGF_LAUNCH_OK();
   return AGGF_OK;
+}
+
+extern "C" int aggf_pair_min(const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype, const void* box,
+                             int32_t box_stride, int square, void* out, void* ws, size_t ws_bytes, void* stream_v) {
+  return pair_min("aggf_pair_min", X, C, T, m, n, dtype, box, box_stride, false, square, out, ws, ws_bytes, stream_v);
+}
+
+extern "C" int aggf_pair_min_cell(const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype,
+                                  const void* cell, int square, void* out, void* ws, size_t ws_bytes, void* stream_v,
+                                  int images) {
+  if (!cell) return fail(AGGF_ERR_ARG, "aggf_pair_min_cell: NULL cell");
+  if (images != AGGF_IMAGES_BRICK && images != AGGF_IMAGES_NEAREST)
+    return fail(AGGF_ERR_ARG, "aggf_pair_min_cell: images %d is neither AGGF_IMAGES_BRICK nor AGGF_IMAGES_NEAREST", images);
+  return pair_min("aggf_pair_min_cell", X, C, T, m, n, dtype, cell, 9, images == AGGF_IMAGES_NEAREST, square, out, ws,
+                  ws_bytes, stream_v);
 }

@@ -325,9 +325,24 @@ int main() {
               if (wsh <= WS)
                 RUNS(aggf_gauss_shift(p, xd, p, fd, T, n, d, S, 0.25, box, stride, d + 4096, d + 8192, ws, wsh, nullptr));
             }
+            for (int images : {AGGF_IMAGES_BRICK, AGGF_IMAGES_NEAREST}) {  // the `_cell` entries: the same plans
+              if (fd == 0 && S == 1)
+                RUNS(aggf_gauss_pair_forces_cell(p, T, n, xd, 37.0, 0.25, p, p, nullptr, nullptr, 0, nullptr, images));
+              if (wpj <= WS) RUNS(aggf_gauss_proj_cell(p, xd, p, fd, T, n, d, S, 0.25, p, d + 4096, ws, wpj, nullptr, images));
+              if (wsh <= WS)
+                RUNS(aggf_gauss_shift_cell(p, xd, p, fd, T, n, d, S, 0.25, p, d + 4096, d + 8192, ws, wsh, nullptr, images));
+            }
             RUNS(aggf_dot(p, xd, (char*)p + 4096, fd, T * n * 3, d, ws, aggf_dot_workspace_bytes(), nullptr));
           }
       }
+  // the `_cell` entries of K7: no cell, an image selector that is neither of the two
+  REFUSED(aggf_gauss_pair_forces_cell(p, 10, 5, 1, 1.0, 0.5, nullptr, p, nullptr, ws, WS, nullptr, AGGF_IMAGES_NEAREST));
+  REFUSED(aggf_gauss_pair_forces_cell(p, 10, 5, 1, 1.0, 0.5, p, p, nullptr, ws, WS, nullptr, 2));
+  REFUSED(aggf_gauss_proj_cell(p, 1, p, 1, 10, 5, d, 4, 0.5, nullptr, d, ws, WS, nullptr, AGGF_IMAGES_NEAREST));
+  REFUSED(aggf_gauss_proj_cell(p, 1, p, 1, 10, 5, d, 4, 0.5, p, d, ws, WS, nullptr, -1));
+  REFUSED(aggf_gauss_shift_cell(p, 1, p, 1, 10, 5, d, 4, 0.5, nullptr, d, d + 4096, ws, WS, nullptr, AGGF_IMAGES_BRICK));
+  REFUSED(aggf_gauss_shift_cell(p, 1, p, 1, 10, 5, d, 4, 0.5, p, d, d + 4096, ws, WS, nullptr, 9));
+  REFUSED(aggf_gauss_proj_cell(p, 1, p, 1, 10, 5, d, 4, 0.0, p, d, ws, WS, nullptr, AGGF_IMAGES_NEAREST));  // width
   // K8: the workspace query over a grid of shapes, refusals, and plausible calls with the queried workspace
   for (int64_t T : Ts)
     for (int32_t N : Ns) sink += aggf_trjdot_cross_workspace_bytes(T, N / 16 + 1, N, 1) + aggf_trjdot_cross_workspace_bytes(T, N, N, 0);
@@ -475,6 +490,30 @@ int main() {
                                                  deg, 65 - deg, T, m, n, P, in, p, bs, sel & 1 ? d : nullptr,
                                                  sel & 2 ? d + 4096 : nullptr, od, nullptr));
             }
+  // the `_cell` entries of K9c / K9d / K9e: no cell, a bad image selector, and the plans of box_stride 9 in both forms
+  REFUSED(aggf_pair_list_dist_cell(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, nullptr, d, nullptr, AGGF_IMAGES_NEAREST));
+  REFUSED(aggf_pair_list_dist_cell(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, p, d, nullptr, 2));
+  REFUSED(aggf_pair_list_dist_cell(p, p, nullptr, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DIST, p, d, nullptr, 9));  // no stride here
+  REFUSED(aggf_pair_list_dist_cell(p, p, p, nullptr, i32, 7, 3, 5, 9, 1, AGGF_PAIR_DOT, p, d, nullptr, AGGF_IMAGES_NEAREST));
+  REFUSED(aggf_pair_list_pull_cell(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, nullptr, d, d, 1, nullptr, AGGF_IMAGES_NEAREST));
+  REFUSED(aggf_pair_list_pull_cell(p, nullptr, p, p, i32, i32, i32, i32, i32, 2, 2, 7, 3, 5, 9, 1, p, d, d, 1, nullptr, -1));
+  REFUSED(aggf_pair_min_cell(p, p, 7, 3, 5, 1, nullptr, 0, d, ws, WS, nullptr, AGGF_IMAGES_NEAREST));
+  REFUSED(aggf_pair_min_cell(p, p, 7, 3, 5, 1, p, 0, d, ws, WS, nullptr, 3));
+  REFUSED(aggf_pair_min_cell(p, p, 1000, 3, 5, 1, p, 0, d, ws, 0, nullptr, AGGF_IMAGES_NEAREST));  // split frames, no workspace
+  RUNS(aggf_pair_min_cell(nullptr, nullptr, 0, 3, 5, 1, p, 0, nullptr, nullptr, 0, nullptr, AGGF_IMAGES_NEAREST));
+  for (int images : {AGGF_IMAGES_BRICK, AGGF_IMAGES_NEAREST})
+    for (int64_t T : {(int64_t)1, (int64_t)67, (int64_t)2000})
+      for (int32_t n : {1, 65, 257})
+        for (int in = 0; in < 2; ++in) {
+          for (int mode : {AGGF_PAIR_DIST, AGGF_PAIR_SQDIST, AGGF_PAIR_DOT})
+            RUNS(aggf_pair_list_dist_cell(p, (char*)p + 4096, p, (char*)p + 4096, i32, T, 17, n, 65, in, mode, p, d, nullptr, images));
+          for (int od = 0; od <= in; ++od)
+            for (int32_t deg : {0, 33})
+              RUNS(aggf_pair_list_pull_cell(p, deg ? p : nullptr, p, (char*)p + 4096, i32, i32, i32, i32, i32, deg, 65 - deg, T,
+                                            17, n, 65, in, p, d, d + 4096, od, nullptr, images));
+          const size_t wm = aggf_pair_min_workspace_bytes(T, 17, n, in);
+          if (wm <= WS) RUNS(aggf_pair_min_cell(p, (char*)p + 4096, T, 17, n, in, p, in, d, ws, wm, nullptr, images));
+        }
   // K9e: the workspace query over the grid of shapes (overflowing ones included), refusals, empty shapes, and plausible
   // calls, open and under a box, with the queried workspace (one split and many)
   for (int64_t T : Ts)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _kernels as K
-from ._cell import Cell, is_cell_rows
+from ._cell import Cell, is_cell_rows, is_nearest, nearest_of
 
 _FACTOR_MSG = "Factor matrix is an incompatible shape."
 
@@ -148,10 +148,11 @@ def _as_box(box, n_steps: int) -> torch.Tensor:
     return box
 
 
-def _wrap(disp: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
+def _wrap(disp: torch.Tensor, box: torch.Tensor, near: bool = False) -> torch.Tensor:
     """The minimum image of displacements (T, ..., 3) in plain torch: d - L rint(d / L), rint to nearest even.  Under
     the (T, 9) rows of a ``Cell``: its brick reduction (``_cell``) in the same plain operations, stage by stage on
-    the updated displacement -- with zero off-diagonal entries the box form's numbers bit for bit (d - 0 k == d)."""
+    the updated displacement -- with zero off-diagonal entries the box form's numbers bit for bit (d - 0 k == d).
+    ``near`` (with the rows of a cell): then the shortest of the brick image's 27 translates (``_cell.nearest_of``)."""
     L = box.to(device=disp.device, dtype=disp.dtype if disp.dtype.is_floating_point else torch.float64)
     if is_cell_rows(L):
         h = L.reshape((L.shape[0],) + (1,) * (disp.dim() - 2) + (9,))
@@ -163,6 +164,8 @@ def _wrap(disp: torch.Tensor, box: torch.Tensor) -> torch.Tensor:
         d1, d0 = d1 - by * kb, d0 - bx * kb
         ka = torch.round(d0 / ax)
         d0 = d0 - ax * ka
+        if near:
+            d0, d1, d2 = nearest_of(d0, d1, d2, ax, bx, by, cx, cy, cz)
         return torch.stack([d0, d1, d2], dim=-1)
     if L.dim() == 2:
         L = L.reshape((L.shape[0],) + (1,) * (disp.dim() - 2) + (3,))
@@ -255,14 +258,18 @@ class PairList:
         ``PairList`` or a (k, 2) integer array): pairs to leave out, e.g. bonded ones; in the self form (i, j) and
         (j, i) are the same pair.  Under a box the minimum image is only the nearest image up to half a box length:
         a cutoff beyond half the smallest length of any frame raises ``ValueError``.  Under a ``pbc.Cell`` the list
-        is exact for ``cutoff <= cell.safe_radius``: a host cell with a larger cutoff raises ``ValueError``; with a cell
-        on a GPU (not read back) that condition is the caller's part."""
+        is exact for ``cutoff <= cell.image_radius`` (``safe_radius`` for brick images, half the shortest lattice
+        vector for ``images="nearest"``): a host cell with a larger cutoff raises ``ValueError``; with a cell on a GPU
+        (not read back) that condition is the caller's part."""
         cutoff = float(cutoff)
         if not cutoff >= 0 or not np.isfinite(cutoff):
             raise ValueError(f"cutoff must be a non-negative finite number; got {cutoff}")
         dmin = min_distances(xyz, cross_xyz, box=box)
         if isinstance(box, Cell):
-            if not box.is_cuda and not cutoff <= box.safe_radius:
+            if box.nearest and not box.is_cuda and not cutoff <= box.image_radius:
+                raise ValueError(f"cutoff {cutoff} is beyond the cell's image radius, half its shortest lattice "
+                                 f"vector = {box.image_radius}: the nearest of 27 images is not the minimum image there")
+            if not box.nearest and not box.is_cuda and not cutoff <= box.safe_radius:
                 raise ValueError(f"cutoff {cutoff} is beyond the cell's safe radius min(ax, by, cz) / 2 = "
                                  f"{box.safe_radius}: the brick image is not the nearest image there")
         elif box is not None:
@@ -313,7 +320,9 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False, box=None) -
     for distances up to half a box length -- on the box forms of the same kernels.  A ``pbc.Cell`` (a triclinic
     cell): every displacement is its brick image -- the nearest image for distances up to ``cell.safe_radius``, a
     periodic image that is never shorter than it beyond -- on the triclinic forms of the same kernels, with every
-    convention of the box forms (inputs, dtypes, gradients of any order, NaN for a bad frame)."""
+    convention of the box forms (inputs, dtypes, gradients of any order, NaN for a bad frame).  A cell with
+    ``images="nearest"``: the shortest of the brick image's 27 translates -- the nearest image for distances up to
+    ``cell.image_radius`` -- on the nearest-image forms of the same kernels; the backward kernels choose the same image."""
     def shape_of(a):
         return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
 
@@ -328,6 +337,7 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False, box=None) -
     if (plist.n_sites, plist.n_cross) != (n_sites, n_cross):
         raise ValueError(f"a pair list for n_sites {plist.n_sites}, n_cross {plist.n_cross} with xyz {shapes[0]}"
                          + ("" if cross_xyz is None else f" and cross_xyz {shapes[1]}"))
+    near = is_nearest(box)
     if box is not None:
         box = _as_box(box, shapes[0][0])
     if _on_kernels(xyz) and (cross_xyz is None or _on_kernels(cross_xyz, xyz)):
@@ -336,6 +346,9 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False, box=None) -
         K.lib()
         if box is None:
             return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square))
+        if near:
+            return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square),
+                                      box.to(xyz.device), True)
         return PairListDist.apply(xyz, xyz if cross_xyz is None else cross_xyz, plist, bool(square),
                                   box.to(xyz.device))
     xyz = xyz if isinstance(xyz, torch.Tensor) else torch.as_tensor(np.asarray(xyz))
@@ -347,7 +360,7 @@ def pair_distances(xyz, pairs, cross_xyz=None, square: bool = False, box=None) -
     j = torch.from_numpy(plist.pairs[:, 1].copy()).to(xyz.device)
     disp = xyz[:, j] - other[:, i]
     if box is not None:
-        disp = _wrap(disp, box)
+        disp = _wrap(disp, box, near)
     return (disp**2).sum(dim=-1) if square else torch.linalg.vector_norm(disp, dim=-1)
 
 
@@ -373,7 +386,8 @@ def min_distances(xyz, cross_xyz=None, square: bool = False, box=None) -> torch.
         c = x if cross_xyz is None else cross_xyz.detach()
         ct = torch.promote_types(x.dtype, c.dtype)
         x, c = x.to(ct).contiguous(), c.to(ct).contiguous()
-        return K.pair_min(x, c, bool(square), None if box is None else box.to(device=x.device, dtype=ct).contiguous())
+        return K.pair_min(x, c, bool(square), None if box is None else box.to(device=x.device, dtype=ct).contiguous(),
+                          near=is_nearest(given))
     with torch.no_grad():
         d = _distances(xyz, cross_xyz, True, False, square, given)
         if d.shape[0] == 0:
@@ -435,7 +449,7 @@ def _distances(xyz, cross_xyz, return_matrix, return_displacements, square, box)
         cross_xyz = cross_xyz if isinstance(cross_xyz, torch.Tensor) else torch.as_tensor(np.asarray(cross_xyz))
         disp = xyz[:, None, :, :] - cross_xyz[:, :, None, :]
     if box is not None:
-        disp = _wrap(disp, _as_box(box, xyz.shape[0]))
+        disp = _wrap(disp, _as_box(box, xyz.shape[0]), is_nearest(box))
     if return_displacements:
         return disp
     if square:

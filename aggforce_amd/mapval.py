@@ -16,7 +16,8 @@ with the offsets and the generator state of the open call.  The field of an open
 whenever a site crosses a face of the cell: it is not a function of the periodic configuration, and a projection on it
 says nothing about the map.  The single-field forms that take a box are ``pbc.sq_gaussian_energies``,
 ``pbc.sq_gaussian_forces`` and ``pbc.rsqpg_forces`` (the names of this module keep the reference's signatures).
-``outer`` must not exceed half the smallest box length (``Cell.safe_radius`` for a cell): beyond it the image switches
+``outer`` must not exceed half the smallest box length (``Cell.safe_radius`` for a cell, ``Cell.image_radius`` for a cell
+with ``images="nearest"``, whose displacements are the nearest of 27 images: ``pbc``): beyond it the image switches
 where the field is not small and the field is discontinuous.  That is checked for a box on the host (``ValueError``,
 before any device work) and not for a box on a GPU (no synchronisation).  The Gaussian's tail past ``outer`` is the
 caller's concern: choose ``width`` so that it has decayed at the switching distance.
@@ -33,7 +34,7 @@ import numpy as np
 import numpy.random as r
 
 from . import _kernels as K
-from ._cell import is_cell_rows
+from ._cell import is_cell_rows, is_nearest
 from .jaxutil import _as_box
 
 _FAST_KWARGS = frozenset({"inner", "outer", "width", "sq_args", "box"})
@@ -116,14 +117,21 @@ def _draw_offsets(randg: r.Generator, n_samples: int, inner, outer, width, sq_ar
 def _host_box(box, n_frames: int, outer=None, sq_args: bool = True):
     """``box`` normalised (``jaxutil._as_box``: (3,), (n_frames, 3) or the (n_frames, 9) rows of a ``Cell``), or None.
     On the host, ``outer`` (if given) as a distance (its square root if it was given squared) must not exceed half the
-    smallest length, ``Cell.safe_radius`` for a cell (``ValueError``); a box on a GPU is not read."""
+    smallest length, ``Cell.safe_radius`` for a cell, ``Cell.image_radius`` for a cell with ``images="nearest"``
+    (``ValueError``); a box on a GPU is not read."""
     if box is None:
         return None
+    given = box
     box = _as_box(box, n_frames)
     if outer is not None and not box.is_cuda and box.numel():
+        reach = float(outer) if sq_args else float(outer) ** 0.5
+        if is_nearest(given):
+            if reach > given.image_radius:
+                raise ValueError(f"outer reaches {reach:g}, beyond the cell's image radius, half its shortest lattice "
+                                 f"vector ({given.image_radius:g}): the field is discontinuous where the image switches")
+            return box
         lengths = box[:, [0, 4, 8]] if is_cell_rows(box) else box
         half = float(lengths.min()) / 2
-        reach = float(outer) if sq_args else float(outer) ** 0.5
         if reach > half:
             raise ValueError(f"outer reaches {reach:g}, beyond half the smallest box length ({half:g}): the field is "
                              "discontinuous where the image switches")
@@ -149,6 +157,7 @@ def _fused(coords, forces, n_samples: int, randg, kwargs, shift: bool) -> List[f
 
     kwargs = dict(kwargs)
     box = kwargs.pop("box", None)
+    near = is_nearest(box)
     if box is not None:
         box = _host_box(box, _shape_of(coords)[0], kwargs.get("outer"), kwargs.get("sq_args", True))
     offsets, width = _draw_offsets(randg, n_samples, **kwargs)
@@ -156,6 +165,8 @@ def _fused(coords, forces, n_samples: int, randg, kwargs, shift: bool) -> List[f
     F = K.as_device(forces)
     o = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float64)).to(X.device)
     under = {} if box is None else {"box": _device_box(box, X)}
+    if near:
+        under["near"] = True
     if shift:
         ip, gsq = (v.cpu().numpy() for v in K.gauss_shift(X, F, o, width, **under))
         vals = (gsq - 2.0 * ip) / float(F.numel())

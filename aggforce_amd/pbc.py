@@ -40,6 +40,13 @@ forms of the same kernels.  The image of a displacement is its brick reduction (
 
 and the image counts (T, N, 3) are those of a, b, c in that order.  Bonds must be shorter than ``safe_radius``.
 
+``Cell(vectors, images="nearest")``: the pair-distance, cutoff-list and map-validation functions then take the shortest
+of the brick image's 27 translates -- for a reduced cell the true minimum image up to ``Cell.image_radius``, half the
+shortest lattice vector (0.5 d in a rhombic dodecahedron or truncated octahedron of image distance d, where
+``safe_radius`` is 0.354 d to 0.408 d): ``_cell``.  ``make_whole``, ``guess_pairwise_constraints``,
+``project_forces(..., box=, bonds=)`` and ``project_forces_grid_cv`` accept such a cell and run their brick forms: they
+measure bonds and rigid pairs, which must be shorter than ``safe_radius`` anyway, and there the two images coincide.
+
 Map validation (``jaxmapval``) under a box: ``random_force_proj(..., box=B)`` and ``random_residual_shift(..., box=B)``
 take the fused periodic path; the single-field functions that take a box are here, ``sq_gaussian_energies``,
 ``sq_gaussian_forces`` and ``rsqpg_forces`` (``jaxmapval`` keeps the reference's signatures, which have no box).
@@ -54,7 +61,7 @@ import torch
 
 from . import _kernels as K
 from . import mapval as _mv
-from ._cell import Cell, cell_good, is_cell_rows  # noqa: F401  (Cell: part of this module's surface)
+from ._cell import Cell, cell_good, is_cell_rows, is_nearest  # noqa: F401  (Cell: part of this module's surface)
 from .jaxutil import PairList, _as_box
 
 MAX_DEPTH = 1 << 16  # a forest this deep is refused: the int32 image counts of K11 cannot overflow below it
@@ -298,7 +305,8 @@ def make_whole(xyz, box, tree, *, inplace: bool = False, return_images: bool = F
 
     ``box``: the lengths of an orthorhombic cell, (3,) or (n_steps, 3), as everywhere (``jaxutil``): a box on the host
     is checked, a box on a GPU is not -- a length that is not positive and finite makes its frame's coordinates NaN
-    (image counts 0) and no other frame's.  A ``Cell``: a triclinic cell -- every atom at the brick image of its
+    (image counts 0) and no other frame's.  A ``Cell`` (with either setting of ``images``: bonds must be shorter than
+    ``safe_radius``, where the nearest image is the brick image): a triclinic cell -- every atom at the brick image of its
     parent, the image counts those of a, b, c in that order (the module's text), a bad frame NaN in every
     component.  ``tree``: a ``MoleculeTree`` (or bonds: a ``PairList`` / (k, 2) array,
     turned into one).  A non-finite coordinate stays where it is and moves nothing else.
@@ -385,21 +393,24 @@ class _HostWhole(torch.autograd.Function):
 
 # ------------------------------------------------------------------ map validation under a box (mapval.py, K7)
 def _mapval_inputs(positions, width, box, outer=None, sq_args: bool = True):
-    """(coordinates on the device, box on the device or None), every argument checked before any device work."""
+    """(coordinates on the device, the ``box`` / ``near`` keywords of the K7 calls), every argument checked before any
+    device work."""
     n_frames = _mv._check_trajectory(positions, "positions")[0]
     _mv._check_width(width)
+    near = is_nearest(box)
     box = _mv._host_box(box, n_frames, outer, sq_args)
     X = K.as_device(positions)
-    return X, _mv._device_box(box, X)
+    return X, ({"box": _mv._device_box(box, X), "near": True} if near else {"box": _mv._device_box(box, X)})
 
 
 def sq_gaussian_energies(positions, offset: float, width: float, box):
     """``jaxmapval.sq_gaussian_energies`` under a periodic box: ``E_t = sum_{i,j} exp(-((|d_ij|^2 - offset) / width)^2)``
     with ``d_ij`` the image of ``r_i - r_j`` under ``box`` -- the lengths of an orthorhombic box, (3,) or
-    (n_frames, 3) (minimum image), or a ``Cell`` (brick image) -- diagonal included (``d = 0``).  Shape (n_frames,),
+    (n_frames, 3) (minimum image), or a ``Cell`` (brick image, or the nearest image with ``images="nearest"``) -- diagonal
+    included (``d = 0``).  Shape (n_frames,),
     in the container and dtype of ``positions``.  A box on a GPU is not checked: a frame whose box is bad is NaN."""
     X, b = _mapval_inputs(positions, width, box)
-    _, E = K.gauss_pair_forces(X, offset, width, want_forces=False, want_energies=True, box=b)
+    _, E = K.gauss_pair_forces(X, offset, width, want_forces=False, want_energies=True, **b)
     return K.like_input(E, positions)
 
 
@@ -408,7 +419,7 @@ def sq_gaussian_forces(positions, offset: float, width: float, box):
     ``x_ij = |d_ij|^2``, ``d_ij`` the image of ``r_i - r_j`` under ``box`` (as ``sq_gaussian_energies``) -- the forces
     of that energy wherever no pair sits where its image switches."""
     X, b = _mapval_inputs(positions, width, box)
-    G, _ = K.gauss_pair_forces(X, offset, width, box=b)
+    G, _ = K.gauss_pair_forces(X, offset, width, **b)
     return K.like_input(G, positions)
 
 
@@ -416,13 +427,13 @@ def rsqpg_forces(positions, inner: float, outer: float, width: float, randg=None
     """``jaxmapval.rsqpg_forces`` with ``box=``: the forces of one random squared-distance Gaussian field of image
     distances (the same draw from ``randg``).  As ``method`` of ``random_force_proj`` / ``random_residual_shift`` it
     takes their fused path.  ``outer`` (a distance if ``sq_args``, else a squared one) must not exceed half the
-    smallest box length, ``Cell.safe_radius`` for a cell: ``ValueError`` for a box on the host, not checked for a box
-    on a GPU.  The Gaussian's tail past ``outer`` is the caller's concern."""
+    smallest box length, ``Cell.safe_radius`` for a cell, ``Cell.image_radius`` for one with ``images="nearest"``:
+    ``ValueError`` for a box on the host, not checked for a box on a GPU.  The Gaussian's tail past ``outer`` is the caller's concern."""
     _mv._check_trajectory(positions, "positions")
     lo, interval_width, w = _mv._sq_params(inner, outer, width, sq_args)
     X, b = _mapval_inputs(positions, w, box, outer, sq_args)
     if randg is None:
         randg = np.random.default_rng()
     offset = randg.random() * interval_width + lo
-    G, _ = K.gauss_pair_forces(X, offset, w, box=b)
+    G, _ = K.gauss_pair_forces(X, offset, w, **b)
     return K.like_input(G, positions)

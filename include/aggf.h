@@ -581,6 +581,26 @@ int aggf_pair_list_pull(const void* W, const void* Dv, const void* X, const void
  *   Frames may be split over workgroups, the partial minima going through ws: ws_bytes >= the
  *   query's value for the same (T, m, n, dtype) (0 when one split suffices; ws may then be
  *   NULL).  No atomics.  T, m or n zero returns AGGF_OK without a launch and without writing.
+ *
+ * THE `_cell` ENTRIES (aggf_pair_list_dist_cell, aggf_pair_list_pull_cell, aggf_pair_min_cell, and
+ * aggf_gauss_pair_forces_cell / aggf_gauss_proj_cell / aggf_gauss_shift_cell of K7): the arguments,
+ * plans, workspaces and conventions of the entry of the same name with box_stride 9, with `cell`
+ * (T, 9) in place of (box, box_stride) (NULL: AGGF_ERR_ARG) and, after the stream, the image
+ * selector `images`: AGGF_IMAGES_BRICK, the brick image above (the kernels of box_stride 9), or
+ * AGGF_IMAGES_NEAREST (any other value: AGGF_ERR_ARG).  The entries that take box_stride keep
+ * their meaning of 0, 3 and 9 and keep refusing every other stride.
+ * NEAREST IMAGE: u is the brick image above, then the shortest of its 27 translates
+ * u + i a + j b + k c, i, j, k in {-1, 0, 1}, by squared length q = fma(z, z, fma(y, y, x x)).
+ * The candidates are visited with (0, 0, 0) first, then k = -1, 0, 1 outermost, j inside it, i
+ * innermost; a candidate replaces the best so far only if it is strictly shorter, so a tie keeps
+ * the earlier one.  A translate is formed as
+ *     x = fma(i, ax, fma(j, bx, fma(k, cx, dx)));  y = fma(j, by, fma(k, cy, dy));  z = fma(k, cz, dz)
+ * (a zero count adds nothing).  A brick image with q <= min(ax, by, cz)^2 / 4 is the answer and
+ * the search is skipped (no lattice vector is shorter than min(ax, by, cz)): the same bits.
+ * For a reduced cell, |bx| <= ax/2, |cx| <= ax/2, |cy| <= by/2, the result is the true minimum
+ * image whenever that image is shorter than half the shortest of the 26 vectors i a + j b + k c;
+ * beyond that it is a periodic image never longer than the brick image.  With zero off-diagonal
+ * entries the results are those of box_stride 3 bit for bit.  Bad frames are NaN as above.
  * ------------------------------------------------------------------------- */
 int aggf_pair_list_dist_pbc(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
                             int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, const void* box,
@@ -593,6 +613,18 @@ int aggf_pair_list_pull_pbc(const void* W, const void* Dv, const void* X, const 
 size_t aggf_pair_min_workspace_bytes(int64_t T, int32_t m, int32_t n, int dtype);
 int aggf_pair_min(const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype, const void* box,
                   int32_t box_stride, int square, void* out, void* ws, size_t ws_bytes, void* stream);
+#define AGGF_IMAGES_BRICK 0
+#define AGGF_IMAGES_NEAREST 1
+int aggf_pair_list_dist_cell(const void* X, const void* C, const void* V, const void* Y, const int32_t* pairs,
+                             int64_t T, int32_t m, int32_t n, int64_t P, int dtype, int mode, const void* cell,
+                             void* out, void* stream, int images);
+int aggf_pair_list_pull_cell(const void* W, const void* Dv, const void* X, const void* C, const int32_t* pairs,
+                             const int32_t* a_ptr, const int32_t* a_idx, const int32_t* b_ptr,
+                             const int32_t* b_idx, int32_t max_deg_a, int32_t max_deg_b, int64_t T, int32_t m,
+                             int32_t n, int64_t P, int in_dtype, const void* cell, void* A, void* B, int out_dtype,
+                             void* stream, int images);
+int aggf_pair_min_cell(const void* X, const void* C, int64_t T, int32_t m, int32_t n, int dtype, const void* cell,
+                       int square, void* out, void* ws, size_t ws_bytes, void* stream, int images);
 
 /* ---------------------------------------------------------------------------
  * K10  The clipped Gaussian radial basis of qp/jaxfeat.py and its derivatives of any order
@@ -848,6 +880,10 @@ int aggf_scale(const void* x, int64_t count, int dtype, double alpha, void* out,
  * frame, (T, 9) (stride 9: brick reduction, the true minimum image up to min(ax, by, cz) / 2).  A frame whose box or
  * cell is bad (a length or diagonal entry that is not positive and finite, an off-diagonal entry that is not finite)
  * has NaN G and E, and makes every out[s], ip[s] and gsq[s] NaN.  Plans and workspaces do not depend on the box.
+ * aggf_gauss_pair_forces_cell / aggf_gauss_proj_cell / aggf_gauss_shift_cell: the same with `cell` (T, 9) in place of
+ * (box, box_stride) and, after the stream, `images` as in K9's section: AGGF_IMAGES_BRICK (d as with box_stride 9) or
+ * AGGF_IMAGES_NEAREST (the true minimum image of a reduced cell up to half its shortest lattice vector); the workspace
+ * queries are those of the entries above.
  * ------------------------------------------------------------------------- */
 size_t aggf_gauss_pair_forces_workspace_bytes(int64_t T, int32_t n);
 int aggf_gauss_pair_forces(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
@@ -861,6 +897,14 @@ size_t aggf_gauss_shift_workspace_bytes(int64_t T, int32_t n, int64_t S);
 int aggf_gauss_shift(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
                      const double* offsets, int64_t S, double width, const void* box, int32_t box_stride, double* ip,
                      double* gsq, void* ws, size_t ws_bytes, void* stream);
+int aggf_gauss_pair_forces_cell(const void* X, int64_t T, int32_t n, int dtype, double offset, double width,
+                                const void* cell, void* G, void* E, void* ws, size_t ws_bytes, void* stream, int images);
+int aggf_gauss_proj_cell(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                         const double* offsets, int64_t S, double width, const void* cell, double* out, void* ws,
+                         size_t ws_bytes, void* stream, int images);
+int aggf_gauss_shift_cell(const void* X, int x_dtype, const void* F, int f_dtype, int64_t T, int32_t n,
+                          const double* offsets, int64_t S, double width, const void* cell, double* ip, double* gsq,
+                          void* ws, size_t ws_bytes, void* stream, int images);
 size_t aggf_dot_workspace_bytes(void);
 int aggf_dot(const void* a, int a_dtype, const void* b, int b_dtype, int64_t count, double* out, void* ws,
              size_t ws_bytes, void* stream);
