@@ -1,5 +1,6 @@
 """Triclinic periodic cells (not in the reference): the ``Cell`` that every ``box=`` of the pair-distance, cutoff-list,
-whole-molecule and constraint-guess functions takes beside the lengths of an orthorhombic box (``pbc.Cell``).
+whole-molecule, constraint-guess, map-validation and featuriser functions takes beside the lengths of an orthorhombic
+box (``pbc.Cell``).
 
 A cell is three lattice vectors as the rows ``a, b, c`` of a lower-triangular matrix (the GROMACS / MDTraj
 convention)::
@@ -50,13 +51,20 @@ image no longer than ``safe_radius`` is the answer already and the search is ski
   within ``safe_radius`` it is the brick image bit for bit.
 
 The image is a locally constant choice, so gradients are those of the brick form with that image, to any order.  It
-is used by ``pair_distances``, ``distances_in_box``, ``min_distances``, ``PairList.from_cutoff`` and the map-validation
-functions; ``guess_pairwise_constraints`` and ``make_whole`` accept such a cell and run their brick forms (they
-measure bonds and rigid pairs, which must be shorter than ``safe_radius``, where the two images coincide).
+is used by ``pair_distances``, ``distances_in_box``, ``min_distances``, ``PairList.from_cutoff``, the map-validation
+functions and the featuriser (below); ``guess_pairwise_constraints`` and ``make_whole`` accept such a cell and run
+their brick forms (they measure bonds and rigid pairs, which must be shorter than ``safe_radius``, where the two
+images coincide).
 
-Not built under a cell: ``gb_feat`` / ``qp.jaxfeat.gb_subfeat`` (K4), ``comm=`` (frames sharded over ranks), gradients
-with respect to the cell; an exact minimum image beyond ``image_radius``; the nearest image of a cell that is not
-reduced.
+THE FEATURISER.  ``gb_feat(box=Cell)`` -- with the fused fit, the one-pass cross-validation and the fitted map's
+application behind it -- and ``qp.jaxfeat.gb_subfeat`` / ``gb_subfeat_jac`` measure the distance from a mapped site to
+a group mean as the length of the cell's image, brick or nearest (cell forms of the K4 kernels).  A feature is a
+function of the TRUE minimum-image distance only up to ``image_radius``, so a cell on the host whose ``image_radius``
+is less than the featuriser's ``outer`` is refused (``check_reach``); an orthorhombic box needs no such rule, its wrap
+is the minimum image at any distance.  A cell on a GPU is not read on the host.
+
+Not built under a cell: ``comm=`` (frames sharded over ranks), gradients with respect to the cell; minimum-image group
+means; an exact minimum image beyond ``image_radius``; the nearest image of a cell that is not reduced.
 """
 from __future__ import annotations
 
@@ -260,6 +268,21 @@ def refuse_cell(box, who: str) -> None:
     if isinstance(box, Cell):
         raise ValueError(f"{who}: triclinic cells are not built here; it takes the lengths of an orthorhombic box, "
                          "(3,) or (n_steps, 3)")
+
+
+def check_reach(box, outer, who: str) -> None:
+    """``ValueError`` if ``box`` is a ``Cell`` on the host whose image is not the minimum image all the way to
+    ``outer``: ``outer`` must not exceed ``image_radius`` (``safe_radius`` for brick images, half the shortest lattice
+    vector for ``images="nearest"``).  Lengths of an orthorhombic box, a cell on a GPU (not read here) and an ``outer``
+    of None pass."""
+    if not isinstance(box, Cell) or box.is_cuda or outer is None or box.vectors.numel() == 0:
+        return
+    radius = box.image_radius
+    if float(outer) > radius:
+        raise ValueError(f"{who}: outer={float(outer):g} reaches beyond image_radius={radius:g} of the triclinic cell "
+                         f"(images={box.images!r}): past it the cell's image is not the minimum image and the feature "
+                         "would be that of a wrong image"
+                         + ("" if box.nearest else '; Cell(..., images="nearest") reaches half the shortest lattice vector'))
 
 
 def cell_good(rows: torch.Tensor) -> torch.Tensor:

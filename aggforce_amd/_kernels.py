@@ -776,12 +776,24 @@ def _gb_dtype(Pg, cg, centers) -> int:
     return dtype_code(Pg.dtype)
 
 
+def _gb_box(name: str, box, Pg, near: bool):
+    """(stride, images) of the ``box`` of a K4 function: stride as ``_box_arg`` gives it (None without a box), images
+    None for lengths (the ``_pbc`` entry) and IMAGES_BRICK / IMAGES_NEAREST for the (T, 9) rows of a cell (the ``_cell``
+    entry)."""
+    if box is None:
+        return None, None
+    stride = _box_arg(name, box, Pg, cell=True, near=near)
+    return stride, ((IMAGES_NEAREST if near else IMAGES_BRICK) if stride == 9 else None)
+
+
 def gb_channels(Pg, cg, site: int, sizes, n_ch: int, centers, width: float, clip: float,
-                box: Optional[torch.Tensor] = None):
+                box: Optional[torch.Tensor] = None, near: bool = False):
     """(gauss (T, n_ch, n_basis), grad (T, n_ch, n_basis, 3)) of one cg site; see aggf_gb_channels.  ``box`` ((3,) or
     (T, 3), the feature dtype; the same for every K4 function that takes one): distances and directions are those of
-    the minimum image under that orthorhombic box (aggf_gb_channels_pbc); a frame whose box is bad is NaN."""
-    stride = None if box is None else _box_arg("gb_channels", box, Pg)
+    the minimum image under that orthorhombic box (aggf_gb_channels_pbc); a frame whose box is bad is NaN.  (T, 9): the
+    rows of a triclinic cell (``pbc.Cell.rows``), the brick image or, with ``near``, the nearest image
+    (aggf_gb_channels_cell)."""
+    stride, images = _gb_box("gb_channels", box, Pg, near)
     l = lib()
     T, G, _ = Pg.shape
     nb = centers.numel()
@@ -795,6 +807,12 @@ def gb_channels(Pg, cg, site: int, sizes, n_ch: int, centers, width: float, clip
             l.aggf_gb_channels(ptr(Pg), ptr(cg), gd, T, G, cg.shape[1], site, ptr(sizes), n_ch, ptr(centers), nb,
                                float(width), float(clip), ptr(gauss), ptr(grad), stream_ptr()),
             "aggf_gb_channels",
+        )
+    elif images is not None:
+        check(
+            l.aggf_gb_channels_cell(ptr(Pg), ptr(cg), gd, T, G, cg.shape[1], site, ptr(sizes), n_ch, ptr(centers), nb,
+                                    float(width), float(clip), ptr(box), ptr(gauss), ptr(grad), stream_ptr(), images),
+            "aggf_gb_channels_cell",
         )
     else:
         check(
@@ -822,10 +840,10 @@ def gb_regmat(Fg, Pg, cg, site: int, sizes, n_id: int, n_ch: int, centers, width
 
 
 def gb_apply(Fg, Pg, cg, sizes, n_id: int, n_ch: int, centers, width: float, clip: float, coef: torch.Tensor,
-             box: Optional[torch.Tensor] = None):
-    """(T, n_cg, 3) float64: the [id | gb] feature-linear map applied; see aggf_gb_apply, and aggf_gb_apply_pbc for
-    ``box`` (as ``gb_channels``)."""
-    stride = None if box is None else _box_arg("gb_apply", box, Pg)
+             box: Optional[torch.Tensor] = None, near: bool = False):
+    """(T, n_cg, 3) float64: the [id | gb] feature-linear map applied; see aggf_gb_apply, and aggf_gb_apply_pbc /
+    aggf_gb_apply_cell for ``box`` and ``near`` (as ``gb_channels``)."""
+    stride, images = _gb_box("gb_apply", box, Pg, near)
     l = lib()
     T, G, _ = Fg.shape
     n_cg = cg.shape[1]
@@ -840,6 +858,13 @@ def gb_apply(Fg, Pg, cg, sizes, n_id: int, n_ch: int, centers, width: float, cli
                                 ptr(centers), centers.numel(), float(width), float(clip), ptr(coef), coef.shape[1],
                                 ptr(out), stream_ptr()),
                 "aggf_gb_apply",
+            )
+        elif images is not None:
+            check(
+                l.aggf_gb_apply_cell(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg), _gb_dtype(Pg, cg, centers), T, G,
+                                     n_cg, ptr(sizes), n_id, n_ch, ptr(centers), centers.numel(), float(width),
+                                     float(clip), ptr(coef), coef.shape[1], ptr(box), ptr(out), stream_ptr(), images),
+                "aggf_gb_apply_cell",
             )
         else:
             check(
@@ -864,13 +889,13 @@ def gb_compact_coefficients(coef: np.ndarray, n_id: int, device):
 
 
 def gb_apply_cols(Fg, Pg, cg, sizes, n_id: int, centers, width: float, clip: float, compact,
-                  box: Optional[torch.Tensor] = None):
+                  box: Optional[torch.Tensor] = None, near: bool = False):
     """gb_apply from the compact coefficient list of :func:`gb_compact_coefficients`; see aggf_gb_apply_cols, and
-    aggf_gb_apply_cols_pbc for ``box`` (as ``gb_channels``)."""
+    aggf_gb_apply_cols_pbc / aggf_gb_apply_cols_cell for ``box`` and ``near`` (as ``gb_channels``)."""
     coef_id, col_ptr, col_idx, col_val = compact
     T, G, _ = Fg.shape
     n_cg = cg.shape[1]
-    stride = None if box is None else _box_arg("gb_apply_cols", box, Pg)
+    stride, images = _gb_box("gb_apply_cols", box, Pg, near)
     out = torch.empty((T, n_cg, 3), dtype=torch.float64, device=Fg.device)
     if T == 0:
         return out
@@ -882,6 +907,14 @@ def gb_apply_cols(Fg, Pg, cg, sizes, n_id: int, centers, width: float, clip: flo
                                          ptr(col_val), ptr(centers), centers.numel(), float(width), float(clip),
                                          ptr(out), stream_ptr()),
                 "aggf_gb_apply_cols",
+            )
+        elif images is not None:
+            check(
+                lib().aggf_gb_apply_cols_cell(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg),
+                                              _gb_dtype(Pg, cg, centers), T, G, n_cg, ptr(sizes), n_id, ptr(coef_id),
+                                              ptr(col_ptr), ptr(col_idx), ptr(col_val), ptr(centers), centers.numel(),
+                                              float(width), float(clip), ptr(box), ptr(out), stream_ptr(), images),
+                "aggf_gb_apply_cols_cell",
             )
         else:
             check(
@@ -1001,12 +1034,14 @@ def gb_constraint_gram(M2: torch.Tensor, gauss: Optional[torch.Tensor], S: int, 
     return out
 
 
-def gb_distance_range(Pg: torch.Tensor, cg: torch.Tensor, n_ch: int, box: Optional[torch.Tensor] = None):
+def gb_distance_range(Pg: torch.Tensor, cg: torch.Tensor, n_ch: int, box: Optional[torch.Tensor] = None,
+                      near: bool = False):
     """(rmin, rmax) (n_cg, G) float32: range over frames of every channel's distance to every cg site
     (evaluated in float32 whatever the feature dtype: the caller applies a safety margin).  ``box`` (as
     ``gb_channels``, in the dtype of ``Pg``): the range of the minimum-image distances (aggf_gb_distance_range_pbc),
-    none of which exceeds half the cell's diagonal."""
-    stride = None if box is None else _box_arg("gb_distance_range", box, Pg)
+    none of which exceeds half the cell's diagonal; the rows of a cell and ``near``: of the brick- or nearest-image
+    distances (aggf_gb_distance_range_cell)."""
+    stride, images = _gb_box("gb_distance_range", box, Pg, near)
     if Pg.dtype != torch.float32:
         Pg, cg = Pg.to(torch.float32), cg.to(torch.float32)
         box = None if box is None else box.to(torch.float32)
@@ -1018,6 +1053,9 @@ def gb_distance_range(Pg: torch.Tensor, cg: torch.Tensor, n_ch: int, box: Option
         if box is None:
             check(lib().aggf_gb_distance_range(ptr(Pg), ptr(cg), T, G, n_cg, n_ch, ptr(rmin), ptr(rmax), stream_ptr()),
                   "aggf_gb_distance_range")
+        elif images is not None:
+            check(lib().aggf_gb_distance_range_cell(ptr(Pg), ptr(cg), T, G, n_cg, n_ch, ptr(box), ptr(rmin), ptr(rmax),
+                                                    stream_ptr(), images), "aggf_gb_distance_range_cell")
         else:
             check(lib().aggf_gb_distance_range_pbc(ptr(Pg), ptr(cg), T, G, n_cg, n_ch, ptr(box), stride, ptr(rmin),
                                                    ptr(rmax), stream_ptr()), "aggf_gb_distance_range_pbc")
@@ -1025,11 +1063,11 @@ def gb_distance_range(Pg: torch.Tensor, cg: torch.Tensor, n_ch: int, box: Option
 
 
 def gb_regmat_cols(Fg, Pg, cg, site: int, sizes, n_id: int, cols: torch.Tensor, centers, width: float, clip: float,
-                   kbt: float, out: torch.Tensor, box: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   kbt: float, out: torch.Tensor, box: Optional[torch.Tensor] = None, near: bool = False) -> torch.Tensor:
     """Compact regression matrix of one cg site (listed Gaussian columns only); see aggf_gb_regmat_cols, and
-    aggf_gb_regmat_cols_pbc for ``box`` (as ``gb_channels``)."""
+    aggf_gb_regmat_cols_pbc / aggf_gb_regmat_cols_cell for ``box`` and ``near`` (as ``gb_channels``)."""
     T, G, _ = Fg.shape
-    stride = None if box is None else _box_arg("gb_regmat_cols", box, Pg)
+    stride, images = _gb_box("gb_regmat_cols", box, Pg, near)
     with _timed("gb_regmat"):
         if box is None:
             check(
@@ -1039,6 +1077,15 @@ def gb_regmat_cols(Fg, Pg, cg, site: int, sizes, n_id: int, cols: torch.Tensor, 
                                           float(width), float(clip), float(kbt), out.shape[1], ptr(out),
                                           dtype_code(out.dtype), stream_ptr()),
                 "aggf_gb_regmat_cols",
+            )
+        elif images is not None:
+            check(
+                lib().aggf_gb_regmat_cols_cell(ptr(Fg), dtype_code(Fg.dtype), ptr(Pg), ptr(cg),
+                                               _gb_dtype(Pg, cg, centers), T, G, cg.shape[1], site, ptr(sizes), n_id,
+                                               ptr(cols), int(cols.numel()), ptr(centers), centers.numel(),
+                                               float(width), float(clip), float(kbt), out.shape[1], ptr(box), ptr(out),
+                                               dtype_code(out.dtype), stream_ptr(), images),
+                "aggf_gb_regmat_cols_cell",
             )
         else:
             check(
@@ -1350,7 +1397,7 @@ def _pair_list_sites(name: str, x: torch.Tensor, c: torch.Tensor, tab: PairTable
 def _box_arg(name: str, box: torch.Tensor, x: torch.Tensor, cell: bool = False, near: bool = False) -> int:
     """The element stride between the frames of ``box`` (the ``box_stride`` of include/aggf.h): 3 for (T, 3), 0 for
     (3,); a contiguous tensor in the dtype and on the device of ``x``.  ``cell``: the entry also takes (T, 9), a
-    row-major 3 x 3 triclinic cell per frame (``pbc.Cell.rows``), stride 9; the K4 entries do not.  ``near`` (the
+    row-major 3 x 3 triclinic cell per frame (``pbc.Cell.rows``), stride 9.  ``near`` (the
     nearest image of a cell, the ``_cell`` entries with AGGF_IMAGES_NEAREST): ``box`` must be those (T, 9) rows."""
     T = x.shape[0]
     if near and (not isinstance(box, torch.Tensor) or tuple(box.shape) != (T, 9)):

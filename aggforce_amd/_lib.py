@@ -72,6 +72,11 @@ PROTOTYPES = {
     "aggf_gb_apply_pbc": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _dbl, _dbl, _vp, _i32, _vp, _i32, _vp, _vp]),
     "aggf_gb_distance_range_pbc": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "aggf_gb_regmat_cols_pbc": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _i32, _vp, C.c_int, _vp]),
+    "aggf_gb_channels_cell": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, C.c_int]),
+    "aggf_gb_apply_cols_cell": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, C.c_int]),
+    "aggf_gb_apply_cell": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _dbl, _dbl, _vp, _i32, _vp, _vp, _vp, C.c_int]),
+    "aggf_gb_distance_range_cell": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int]),
+    "aggf_gb_regmat_cols_cell": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _dbl, _dbl, _dbl, _i32, _vp, _vp, C.c_int, _vp, C.c_int]),
     "aggf_trjdot_frames": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i32, _i32, _vp, _vp, C.c_int, _vp]),
     "aggf_trjdot_cross_workspace_bytes": (_sz, [_i64, _i32, _i32, C.c_int]),
     "aggf_trjdot_cross": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _vp, C.c_int, C.c_int, _vp, _sz, _vp]),

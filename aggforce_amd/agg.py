@@ -395,8 +395,8 @@ def project_forces_grid_cv(
     ``box`` (extra): as in ``project_forces``, for all ``n_frames`` frames.  The loop hands every training
     subset its box -- a (3,) box as it is, a per-frame box indexed with the training frames -- for the "auto"
     guess.  The one-pass forms take explicit constraints, so the box has no effect on them and does not keep a
-    call from them.  A featuriser's own box (``Curry(gb_feat, ..., box=)``, see ``project_forces``) must be (3,): a
-    per-frame one is refused here, up front, with a ``ValueError`` -- in the one-pass form and in the loop alike, whose
+    call from them.  A featuriser's own box (``Curry(gb_feat, ..., box=)``, see ``project_forces``) must be (3,) or a
+    constant ``pbc.Cell``: a per-frame one is refused here, up front, with a ``ValueError`` -- in the one-pass form and in the loop alike, whose
     training subsets cannot carry it.
 
     ``bonds`` (extra): as in ``project_forces``; needs ``box`` and ``coords``.  All frames are made whole once, before
@@ -408,8 +408,8 @@ def project_forces_grid_cv(
     for featurizer in [kwargs.get("featurizer"), *cv_arg_dict.get("featurizer", [])]:
         if _per_frame(bound_box(featurizer)):
             raise ValueError("project_forces_grid_cv: the featuriser binds a per-frame box (gb_feat(box=) of shape "
-                             "(n_frames, 3)), which the training subsets of a cross-validation cannot carry; bind a "
-                             "(3,) box")
+                             "(n_frames, 3), or a per-frame Cell), which the training subsets of a cross-validation "
+                             "cannot carry; bind a (3,) box or a constant Cell")
     if bonds is not None:
         coords = _whole_coords(coords, box, bonds)
     if box is not None:

@@ -170,6 +170,33 @@ int main() {
       }
       RUNS(aggf_gb_regmat_cols_pbc(p, 0, p, p, 0, 10, 5, 2, 1, fp, 5, i32, 3, p, 10, 1.0, 1e-3, 0.6, 128, p, bs, p, 0, nullptr));
     }
+    // the `_cell` entries: no cell, an image selector that is neither of the two, then both images over the dispatch
+    REFUSED(aggf_gb_channels_cell(p, p, 0, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, nullptr, p, p, nullptr, AGGF_IMAGES_BRICK));
+    REFUSED(aggf_gb_channels_cell(p, p, 0, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, p, p, p, nullptr, 2));
+    REFUSED(aggf_gb_channels_cell(p, p, 7, 10, 5, 2, 0, fp, 4, p, 8, 1.0, 1e-5, p, p, p, nullptr, AGGF_IMAGES_NEAREST));  // dtype
+    REFUSED(aggf_gb_distance_range_cell(fp, fp, 10, 5, 2, 4, nullptr, fp, fp, nullptr, AGGF_IMAGES_NEAREST));
+    REFUSED(aggf_gb_distance_range_cell(fp, fp, 10, 5, 2, 4, fp, fp, fp, nullptr, -1));
+    REFUSED(aggf_gb_distance_range_cell(fp, fp, 10, 5, 2, 6, fp, fp, fp, nullptr, AGGF_IMAGES_BRICK));  // n_ch > G
+    REFUSED(aggf_gb_regmat_cols_cell(p, 0, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, nullptr, p, 1, nullptr, AGGF_IMAGES_BRICK));
+    REFUSED(aggf_gb_regmat_cols_cell(p, 0, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 128, p, p, 1, nullptr, 3));
+    REFUSED(aggf_gb_regmat_cols_cell(p, 0, p, p, 0, 10, 5, 2, 0, fp, 5, i32, 3, p, 8, 1.0, 1e-5, 0.6, 7, p, p, 1, nullptr, AGGF_IMAGES_NEAREST));  // ld_feat
+    REFUSED(aggf_gb_apply_cell(p, 0, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 37, nullptr, d, nullptr, AGGF_IMAGES_NEAREST));
+    REFUSED(aggf_gb_apply_cell(p, 0, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 37, p, d, nullptr, 7));
+    REFUSED(aggf_gb_apply_cell(p, 0, p, p, 0, 10, 5, 2, fp, 5, 4, p, 8, 1.0, 1e-5, d, 36, p, d, nullptr, AGGF_IMAGES_BRICK));  // n_feat
+    REFUSED(aggf_gb_apply_cols_cell(p, 0, p, p, 0, 10, 5, 2, fp, 5, d, i32, i32, d, p, 8, 1.0, 1e-5, nullptr, d, nullptr, AGGF_IMAGES_BRICK));
+    REFUSED(aggf_gb_apply_cols_cell(p, 0, p, p, 0, 10, 5, 2, fp, 5, d, i32, i32, d, p, 8, 1.0, 1e-5, p, d, nullptr, -2));
+    for (int images : {AGGF_IMAGES_BRICK, AGGF_IMAGES_NEAREST}) {
+      RUNS(aggf_gb_distance_range_cell(fp, fp, 10, 5, 2, 4, fp, fp, fp, nullptr, images));
+      for (int gd = 0; gd < 2; ++gd) {
+        RUNS(aggf_gb_channels_cell(p, p, gd, 10, 5, 2, 1, fp, 4, p, 10, 1.0, 1e-3, p, p, p, nullptr, images));
+        for (int fd = 0; fd < 2; ++fd) {
+          RUNS(aggf_gb_regmat_cols_cell(p, fd, p, p, gd, 10, 5, 2, 1, fp, 5, i32, 3, p, 10, 1.0, 1e-3, 0.6, 128, p, p, 1, nullptr, images));
+          RUNS(aggf_gb_apply_cell(p, fd, p, p, gd, 10, 5, 2, fp, 5, 4, p, 10, 1.0, 1e-3, d, 45, p, d, nullptr, images));
+          RUNS(aggf_gb_apply_cols_cell(p, fd, p, p, gd, 10, 5, 2, fp, 5, d, i32, i32, d, p, 10, 1.0, 1e-3, p, d, nullptr, images));
+        }
+      }
+      RUNS(aggf_gb_regmat_cols_cell(p, 0, p, p, 0, 10, 5, 2, 1, fp, 5, i32, 3, p, 10, 1.0, 1e-3, 0.6, 128, p, p, 0, nullptr, images));
+    }
   }
   REFUSED(aggf_trjdot_frames(nullptr, 1, p, 1, 10, 5, 2, nullptr, p, 1, nullptr));
   REFUSED(aggf_feat_contract(nullptr, 0, p, p, 0, 1.0, 10, 5, 7, 128, p, 1, nullptr));

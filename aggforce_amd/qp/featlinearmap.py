@@ -284,6 +284,9 @@ def qp_feat_linear_map(
 
     if constraints is None:
         constraints = set()
+    from .gbfeat import bound_box, refuse_cell_under_comm
+
+    refuse_cell_under_comm(bound_box(featurizer), comm)  # (before any device work)
     fused_fit = getattr(featurizer, "fused_fit", None) if fused else None
     if fused_fit is not None:
         return fused_fit(traj, coord_map, kbt, n_constraint_frames, constraints, l2_regularization,
@@ -321,8 +324,9 @@ def qp_feat_linear_map(
         coefs.append(X[0].cpu().numpy())
         del feat_dev, div_dev, r3, G
     # CLAMap's constructor probes the map with ONE frame of zeros; a featuriser that binds a per-frame box
-    # (gb_feat(box=) of shape (n_frames, 3)) takes trajectories of exactly its own length, so the probe is left out
-    from .gbfeat import _per_frame, bound_box
+    # (gb_feat(box=) of shape (n_frames, 3), or a per-frame Cell) takes trajectories of exactly its own length, so the
+    # probe is left out
+    from .gbfeat import _per_frame
 
     force_map = _feat_linear_mapping(
         featurizer=featurizer,

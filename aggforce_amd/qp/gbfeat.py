@@ -31,6 +31,11 @@ points along the minimum-image displacement (box forms of the K4 kernels).  Boun
 cross-validation ((3,) only) and the fitted map's application.  The box reaches that one displacement
 and nothing else: group means and mapped sites are plain averages of the coordinates as given, so
 constraint groups and beads must be whole (``pbc.make_whole``, ``project_forces(..., bonds=)``).
+
+A ``pbc.Cell`` in place of the lengths is a triclinic cell, brick or nearest images, one for all frames or one per
+frame, on the cell forms of the same kernels (``gb_feat``'s text: a host cell whose ``image_radius`` is less than
+``outer`` is refused).  A constant cell goes wherever a (3,) box goes, a per-frame cell wherever a per-frame box goes;
+with ``comm=`` every ``Cell`` is refused.
 """
 from typing import List, Optional, Tuple
 
@@ -66,16 +71,20 @@ class _Geometry:
     """Device-side per-trajectory quantities shared by all cg sites."""
 
     def __init__(self, coords, cmap: LinearMap, constraints: Constraints, drop_last_channel: bool,
-                 feature_dtype=np.float32, box=None):
+                 feature_dtype=np.float32, box=None, outer=None):
         import torch
 
-        if box is not None:  # shape, and the values of a host box, before any device work
-            from .._cell import refuse_cell
+        self.near = False
+        if box is not None:  # shape, the values of a host box and the reach of a host cell, before any device work
+            from .._cell import check_reach, is_nearest
             from ..jaxutil import _as_box
 
-            refuse_cell(box, "gb_feat")
-
-            box = _as_box(box, coords.shape[0])
+            check_reach(box, outer, "gb_feat")
+            self.near = is_nearest(box)
+            try:
+                box = _as_box(box, coords.shape[0])
+            except ValueError as exc:
+                raise ValueError(f"gb_feat: {exc}") from None
         self.fdt = K.torch_dtype(_feature_dtype(feature_dtype))
         self.ids = constraint_group_labels(cmap.n_fg_sites, constraints)
         self.G = int(self.ids.max()) + 1
@@ -94,7 +103,8 @@ class _Geometry:
         # JAX arrays unless feature_dtype=np.float64 was asked for
         self.Pg = K.group_reduce(c, self.grp_ptr, self.grp_atoms, self.G, True, self.fdt)
         self.cg = K.as_device(cmap(c)).to(self.fdt).contiguous()
-        # the cell, (3,) or (T, 3), in the feature dtype beside them (None: open distances)
+        # the cell -- (3,), (T, 3) or the (T, 9) rows of a ``Cell``, whose image ``near`` names -- in the feature dtype
+        # beside them (None: open distances)
         self.box = None if box is None else box.to(device=self.dev, dtype=self.fdt).contiguous()
         # group-summed coordinate map: sum_a M[c,a] [label(a) == g]
         M = np.asarray(cmap.standard_matrix, dtype=np.float64)
@@ -137,20 +147,30 @@ def gb_feat(
     mapped site to a group mean is then the minimum-image distance, d - L rint(d / L) per component, evaluated in the
     feature dtype, and the divergence points along that displacement.  Nothing else is wrapped: the group means and
     the mapped sites ``cmap(points)`` are plain averages of ``points``, so every constraint group and every bead must
-    be whole -- what ``pbc.make_whole`` / ``project_forces(..., bonds=)`` deliver.  Triclinic cells are not built.
+    be whole -- what ``pbc.make_whole`` / ``project_forces(..., bonds=)`` deliver.
+
+    A ``pbc.Cell`` stands for a triclinic cell, one for all frames or one per frame (``ValueError`` for another number
+    of frames): the displacement is then the cell's image, brick or ``images="nearest"`` (cell forms of the K4 kernels;
+    with zero off-diagonal entries the box form's numbers bit for bit).  That image is the minimum image only up to
+    ``Cell.image_radius`` -- ``safe_radius`` for brick images, half the shortest lattice vector for nearest ones -- so a
+    cell on the host with ``outer > image_radius`` is refused (``ValueError``, before any device work): beyond it the
+    feature would silently be that of a wrong image.  (An orthorhombic wrap is the minimum image at any distance and
+    has no such rule.)  A cell on a GPU is not read on the host: a bad frame comes out NaN, and ``outer`` is the
+    caller's concern, as is the Gaussian's tail past ``outer`` in either case.
     """
     import torch
 
     if div_method not in (DIVMETHOD_REORDER, DIVMETHOD_BASIC):
         raise ValueError("Unknown method for jacobian calculation.")
     fdt = _feature_dtype(feature_dtype)
-    geo = _Geometry(points, cmap, constraints, drop_last_channel, fdt, box)
+    geo = _Geometry(points, cmap, constraints, drop_last_channel, fdt, box, outer)
     centers = torch.from_numpy(gb_centers(outer, inner, n_basis, dist_power, fdt)).to(geo.dev)
     ids_dev = torch.from_numpy(geo.ids.astype(np.int64)).to(geo.dev)
     keep = torch.nonzero(ids_dev < geo.n_ch).flatten()
 
     def site_arrays(site: int):
-        gauss, grad = K.gb_channels(geo.Pg, geo.cg, site, geo.sizes, geo.n_ch, centers, width, CLIP, box=geo.box)
+        gauss, grad = K.gb_channels(geo.Pg, geo.cg, site, geo.sizes, geo.n_ch, centers, width, CLIP, box=geo.box,
+                                     near=geo.near)
         feats = torch.zeros((geo.T, cmap.n_fg_sites, geo.n_ch, n_basis), dtype=geo.fdt, device=geo.dev)
         if keep.numel():
             feats[:, keep, ids_dev[keep], :] = gauss[:, ids_dev[keep], :]
@@ -206,8 +226,29 @@ def recognise(featurizers) -> Optional[Tuple[bool, Optional[dict]]]:
 
 
 def _per_frame(box) -> bool:
-    """Whether a box as a caller gives it has one row per frame (anything two-dimensional; ``_as_box`` judges it)."""
+    """Whether a box as a caller gives it has one row per frame (anything two-dimensional; ``_as_box`` judges it), or
+    is a ``Cell`` with one matrix per frame."""
+    from .._cell import Cell
+
+    if isinstance(box, Cell):
+        return box.is_per_frame
     return box is not None and len(getattr(box, "shape", None) or np.shape(box)) == 2
+
+
+def _box_frames(box) -> int:
+    """The number of frames of a per-frame box or ``Cell``."""
+    from .._cell import Cell
+
+    return int(box.vectors.shape[0]) if isinstance(box, Cell) else len(box)
+
+
+def refuse_cell_under_comm(box, comm, who: str = "gb_feat") -> None:
+    """``ValueError`` for a ``Cell`` bound in the featuriser when the frames are sharded over ranks (not built)."""
+    from .._cell import Cell
+
+    if comm is not None and isinstance(box, Cell):
+        raise ValueError(f"{who}: a triclinic cell (pbc.Cell) bound in the featuriser is not supported with comm= "
+                         "(frames sharded over ranks); fit on one rank")
 
 
 def bound_box(featurizer):
@@ -289,7 +330,7 @@ def _fused_setup(coords, forces, coord_map: LinearMap, constraints: Constraints,
     kw = dict(gb_kwargs or {})
     drop_last = kw.pop("drop_last_channel", True)
     fdt = _feature_dtype(kw.pop("feature_dtype", np.float32))
-    geo = _Geometry(coords, coord_map, constraints, drop_last, fdt, kw.pop("box", None))
+    geo = _Geometry(coords, coord_map, constraints, drop_last, fdt, kw.pop("box", None), kw.get("outer"))
     n_basis = int(kw.get("n_basis", 10)) if gb_kwargs is not None else 1
     width = float(kw.get("width", 1.0))
     centers_h = (gb_centers(kw["outer"], kw.get("inner", 0), n_basis, kw.get("dist_power", 0.5), fdt)
@@ -310,10 +351,11 @@ def _fused_setup(coords, forces, coord_map: LinearMap, constraints: Constraints,
     # the minimiser is exactly 0, so it is left out (for a cut-off basis most columns are: BASELINE config 4
     # keeps ~2100 of 6139).  The distance range per (site, channel) is a superset test -- it can only keep
     # columns that are zero after all, never drop one that is not.  Under a box it is the range of the minimum-image
-    # distances, none of which exceeds half the cell's diagonal: fewer columns can be kept, never more.
+    # distances, none of which exceeds half the cell's diagonal: fewer columns can be kept, never more (under a
+    # ``Cell``: of its image distances, brick or nearest).
     keep = np.ones((n_cg, n_ch * n_basis), dtype=bool)
     if n_ch and COMPACT_ZERO_COLUMNS:
-        rmin, rmax = K.gb_distance_range(geo.Pg, geo.cg, n_ch, box=geo.box)
+        rmin, rmax = K.gb_distance_range(geo.Pg, geo.cg, n_ch, box=geo.box, near=geo.near)
         all_reduce_minmax_(rmin, rmax, comm)
         lo = rmin.cpu().numpy()[:, :n_ch].astype(np.float64)
         hi = rmax.cpu().numpy()[:, :n_ch].astype(np.float64)
@@ -369,10 +411,13 @@ def fit_id_gb(
 ) -> CLAFTMap:
     """qp_feat_linear_map (featlinearmap.py:249-394) for id_feat and/or gb_feat features, fused.  A box bound in the
     featuriser (``gb_feat(box=)``) goes to every kernel that measures the distance; one row per frame is for the frames
-    of ``traj``, and the fitted map then applies to trajectories of exactly that many frames."""
+    of ``traj``, and the fitted map then applies to trajectories of exactly that many frames.  A ``pbc.Cell`` likewise
+    (the sampled constraint frames take their own rows of a per-frame cell); with ``comm=`` every ``Cell`` is refused."""
     import torch
 
     box_given = (gb_kwargs or {}).get("box")
+    outer_given = (gb_kwargs or {}).get("outer")
+    refuse_cell_under_comm(box_given, comm)
     if comm is not None and _per_frame(box_given):
         # (a rank holds a slice of the frames and would need the matching rows, and the sampled constraint frames
         # theirs from the rank that owns them: not built.  A (3,) box needs nothing exchanged.)
@@ -398,8 +443,8 @@ def fit_id_gb(
     flat_idx = np.concatenate(used) if used else np.zeros(0, dtype=np.int64)
     Pg_sel = take_global_frames(geo.Pg, flat_idx, comm)
     cg_sel = take_global_frames(geo.cg, flat_idx, comm)
-    box = geo.box
-    per_frame = box is not None and box.dim() == 2
+    box, near = geo.box, geo.near
+    per_frame = box is not None and box.dim() == 2  # (the rows of a ``Cell`` always are: a constant cell is expanded)
     box_sel = box[torch.as_tensor(flat_idx, device=geo.dev)] if per_frame else box  # the sampled frames' own rows
     sel_begin = np.concatenate([[0], np.cumsum([len(u) for u in used])]).astype(np.int64)
     n_sel = {len(u) for u in used}
@@ -458,7 +503,8 @@ def fit_id_gb(
             R3 = R3s[j % n_str]
             cols = cols_dev[site]
             na = n_act[site]
-            K.gb_regmat_cols(Fg, geo.Pg, geo.cg, site, geo.sizes, n_id, cols, centers, width, CLIP, kbt, R3, box=box)
+            K.gb_regmat_cols(Fg, geo.Pg, geo.cg, site, geo.sizes, n_id, cols, centers, width, CLIP, kbt, R3, box=box,
+                             near=near)
             # float64 products: with float32 products the Gram's rounding noise (~1e-7 of its largest entry)
             # exceeds l2 = 10 relative to force-squared sums of ~1e8 and P is no longer numerically positive
             # definite; the exact Gram of the float32 regression matrix always is
@@ -486,7 +532,7 @@ def fit_id_gb(
             if n_ch:
                 gauss, _ = K.gb_channels(Pg_sel[lo_s:hi_s].contiguous(), cg_sel[lo_s:hi_s].contiguous(), site,
                                          geo.sizes, n_ch, centers, width, CLIP,
-                                         box=box_sel[lo_s:hi_s].contiguous() if per_frame else box_sel)
+                                         box=box_sel[lo_s:hi_s].contiguous() if per_frame else box_sel, near=near)
             # (the constraint kernels stay inside the site loop: issued for all sites ahead of it they run alone,
             # 5 ms per step at BASELINE config 4 -- here they fill the tails of the Gram launches)
             K.gb_constraint_rows(Mg, gauss, S, n_id, n_ch, n_basis, site, out_A=As[j], out_b=bs[j], cols=cols)  # K4b
@@ -534,20 +580,20 @@ def fit_id_gb(
         return (to(coef_h[:, :n_id]) if n_id else None, to(ptr_h), to(np.concatenate(cols_of)), to(vals))
 
     def apply_f(points, copoints):
-        if _per_frame(box_given) and len(box_given) != copoints.shape[0]:
-            raise ValueError(f"this map was fitted with a per-frame box of {len(box_given)} frames and applies to "
-                             f"coordinates of exactly {len(box_given)} frames; got {copoints.shape[0]} (bind a (3,) box "
-                             "in gb_feat to apply a map to other trajectories)")
-        g2 = _Geometry(copoints, coord_map, constraints, drop_last, fdt, box_given)
+        if _per_frame(box_given) and _box_frames(box_given) != copoints.shape[0]:
+            raise ValueError(f"this map was fitted with a per-frame box of {_box_frames(box_given)} frames and applies "
+                             f"to coordinates of exactly {_box_frames(box_given)} frames; got {copoints.shape[0]} (bind "
+                             "a (3,) box or a constant Cell in gb_feat to apply a map to other trajectories)")
+        g2 = _Geometry(copoints, coord_map, constraints, drop_last, fdt, box_given, outer_given)
         key = str(g2.dev)
         if key not in compact:
             compact[key] = compact_on(g2.dev) if sparse else torch.from_numpy(coef_h).to(g2.dev)
         if sparse:
             out = K.gb_apply_cols(g2.group_forces(points), g2.Pg, g2.cg, g2.sizes, n_id, centers.to(g2.dev), width, CLIP,
-                                  compact[key], box=g2.box)
+                                  compact[key], box=g2.box, near=g2.near)
         else:
             out = K.gb_apply(g2.group_forces(points), g2.Pg, g2.cg, g2.sizes, n_id, n_ch, centers.to(g2.dev), width, CLIP,
-                             compact[key], box=g2.box)
+                             compact[key], box=g2.box, near=g2.near)
         return K.like_input(out, points)
 
     from .featlinearmap import _feat_linear_mapping
@@ -578,7 +624,8 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
     kept are those not identically zero over ALL frames, a superset of every training set's (their extra coefficients
     are exact zeros: needs l2 > 0, which the caller checks).
 
-    A (3,) box bound in the featuriser is passed through to every kernel; a per-frame box is refused (the frames are
+    A (3,) box or a constant ``pbc.Cell`` bound in the featuriser is passed through to every kernel; a per-frame box
+    or cell is refused (the frames are
     gathered into fold order here and the loop's training subsets cannot carry it: ``project_forces_grid_cv`` says so
     up front).
 
@@ -587,7 +634,8 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
     import torch
 
     if _per_frame((gb_kwargs or {}).get("box")):
-        raise ValueError("gb_feat: a per-frame box is not supported in cross-validation; bind a (3,) box")
+        raise ValueError("gb_feat: a per-frame box or Cell is not supported in cross-validation; bind a (3,) box or "
+                         "a constant Cell")
     n_folds = len(folds)
     lens = [len(f) for f in folds]
     bounds = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -622,7 +670,7 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
         per_alpha = []
         for alpha in ((float(kbt),) if same else (float(kbt), 1.0)):
             K.gb_regmat_cols(su.Fg, geo.Pg, geo.cg, site, geo.sizes, n_id, cols_dev[site], su.centers, su.width, CLIP,
-                             alpha, R3, box=geo.box)
+                             alpha, R3, box=geo.box, near=geo.near)
             Gf = torch.empty((n_folds, na, na), dtype=torch.float64, device=dev)
             for k in range(n_folds):
                 lead = lead_n if (shared_lead[k] is not None and na >= 256) else 0
@@ -644,6 +692,8 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
     per_batch = _sites_per_batch(n_cg, n_max, S * n_cg, dev)
     batches = _solve_batches(n_act, per_batch) if per_batch > 1 else [[i] for i in range(n_cg)]
     orders = [_solve_order(b, n_act, su.touched, max(n_act[i] for i in b), dev) for b in batches]
+    # the S sampled frames of a site under a constant cell: S of its (identical) rows
+    box_s = geo.box[:S].contiguous() if geo.box is not None and geo.box.dim() == 2 else geo.box
     scores: List[List[Optional[float]]] = []
     for l2 in l2_values:
         row: List[Optional[float]] = []
@@ -670,7 +720,8 @@ def cv_id_gb(coords, forces, coord_map: LinearMap, kbt: float, n_constraint_fram
                     gauss = None
                     if n_ch:
                         gauss, _ = K.gb_channels(Pg_sel[site * S:(site + 1) * S], cg_sel[site * S:(site + 1) * S], site,
-                                                 geo.sizes, n_ch, su.centers, su.width, CLIP, box=geo.box)
+                                                 geo.sizes, n_ch, su.centers, su.width, CLIP, box=box_s,
+                                                 near=geo.near)
                     K.gb_constraint_rows(su.Mg, gauss, S, n_id, n_ch, n_basis, site, out_A=As[j], out_b=bs[j],
                                          cols=cols_dev[site])
                     K.gb_constraint_gram(su.M2, gauss, S, n_id, n_ch, n_basis, AtAs[j], cols=cols_dev[site])

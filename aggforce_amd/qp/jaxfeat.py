@@ -12,6 +12,10 @@ Two conventions differ from JAX on sets of measure zero.  At a zero distance the
 weight 0 (``PairDist``'s convention; JAX gives NaN), and at the tie exp(-z^2) == clip the derivative is 0 (JAX's
 ``maximum`` gives half of it).  Centres, width and clip are constants, as in the reference, where they are Python
 floats under ``jit``.
+
+``box=`` (a keyword of ``gb_subfeat`` / ``gb_subfeat_jac``; not in the reference): the lengths of an orthorhombic box,
+or a ``pbc.Cell`` -- the distances are then those of the cell's image, brick or nearest (``jaxutil.distances_in_box``:
+K9c on the GPU), and a host cell whose ``image_radius`` is less than ``outer`` is refused, as in ``gb_feat``.
 """
 from functools import lru_cache
 from typing import Optional, Tuple, Union
@@ -20,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import _kernels as K
-from .._cell import refuse_cell
+from .._cell import check_reach, is_nearest
 from ..jaxutil import _as_box, _wrap, distances, distances_in_box, trjdot
 from .gbfeat import gb_centers, gb_feat
 
@@ -160,10 +164,12 @@ def gb_subfeat(points, cg_points, channels, max_channels, smear_mat, collapse=Fa
 
     ``box`` (a keyword among ``kwargs``, so that the signature stays the reference's; not in the reference; (3,) or
     (n_frames, 3), a constant; default None): the distances are minimum-image distances under
-    that orthorhombic cell (``jaxutil.distances_in_box``), as ``gb_feat(box=)`` measures them."""
+    that orthorhombic cell (``jaxutil.distances_in_box``), as ``gb_feat(box=)`` measures them.  A ``pbc.Cell``: the
+    image distances of that triclinic cell, brick or nearest; a host cell with ``outer`` beyond its ``image_radius`` is
+    refused (``ValueError``), as in ``gb_feat``."""
     box = kwargs.pop("box", None)
-    refuse_cell(box, "gb_subfeat")
     outer, inner, n_basis, width, dist_power, clip = _basis_kwargs(**kwargs)
+    check_reach(box, outer, "gb_subfeat")
     dummy_axis = len(points.shape) == 2
     if dummy_axis:
         points = points[None, ...]
@@ -197,12 +203,13 @@ def gb_subfeat_jac(points, cg_points, channels, max_channels, smear_mat=None, me
 
     over the channels below ``max_channels``.  At r = 0 the weight is 0 (the reference gives NaN).  Differentiable as
     ``gb_subfeat`` is.  ``box`` (a keyword among ``kwargs``, as in ``gb_subfeat``): u is the minimum-image displacement u - L rint(u / L) and r its
-    length."""
+    length; under a ``pbc.Cell`` u is the cell's image of the displacement, brick or nearest (``_cell.nearest_of``), with
+    the rule on ``outer`` of ``gb_subfeat``."""
     if method not in (DIVMETHOD_BASIC, DIVMETHOD_REORDER):
         raise ValueError("Unknown method for jacobian calculation.")
     box = kwargs.pop("box", None)
-    refuse_cell(box, "gb_subfeat_jac")
     outer, inner, n_basis, width, dist_power, clip = _basis_kwargs(**kwargs)
+    check_reach(box, outer, "gb_subfeat_jac")
     p, cg, r = _site_distances(points, cg_points, smear_mat, box)
     centers = _grid(r.dtype, outer, inner, n_basis, dist_power)
     if _on_kernels(r):
@@ -212,7 +219,7 @@ def gb_subfeat_jac(points, cg_points, channels, max_channels, smear_mat=None, me
     else:
         slope = _plain_basis(r, centers, width, clip, q=1)
     pos = r > 0
-    disp = p - cg if box is None else _wrap(p - cg, _as_box(box, p.shape[0]))  # (rint is locally constant: no gradient)
+    disp = p - cg if box is None else _wrap(p - cg, _as_box(box, p.shape[0]), is_nearest(box))  # (the image is locally constant)
     unit = torch.where(pos[..., None], disp / torch.where(pos, r, torch.ones_like(r))[..., None],
                        torch.zeros_like(p))
     weights = slope[..., None] * unit[:, :, None, :]                            # (T, N, n_basis, 3)

@@ -428,6 +428,36 @@ int aggf_gb_apply_cols_pbc(const void* Fg, int f_dtype, const void* Pg, const vo
                            const void* centers, int32_t n_basis, double width, double clip, const void* box,
                            int32_t box_stride, double* out, void* stream);
 
+/* Cell forms of the same five (the `_cell` convention of K9's section): `cell` (T, 9), the row-major 3 x 3
+ * lower-triangular matrix of every frame (rows a, b, c; a constant cell is expanded by the caller) in g_dtype
+ * (float32 for aggf_gb_distance_range_cell), stands in place of (box, box_stride), and the selector `images` comes
+ * after the stream: AGGF_IMAGES_BRICK -- Pg[t,ch] - cg[t,site] is replaced by its brick image, the true minimum image
+ * up to min(ax, by, cz) / 2 -- or AGGF_IMAGES_NEAREST -- by the shortest of the brick image's 27 translates, for a
+ * reduced cell the true minimum image up to half the shortest lattice vector.  With zero off-diagonal entries both
+ * give the box forms' bits.  A frame whose cell is bad (a diagonal entry that is not positive and finite, a lower
+ * off-diagonal entry that is not finite) is treated as a frame with a bad box length above, and no other frame is
+ * touched.  NULL cell or another value of images: AGGF_ERR_ARG.  The `_pbc` entries keep their strides, 0 and 3. */
+int aggf_gb_channels_cell(const void* Pg, const void* cg, int g_dtype, int64_t T, int32_t G, int32_t n_cg,
+                          int32_t site, const float* sizes, int32_t n_ch, const void* centers,
+                          int32_t n_basis, double width, double clip, const void* cell, void* gauss, void* grad,
+                          void* stream, int images);
+int aggf_gb_distance_range_cell(const float* Pg, const float* cg, int64_t T, int32_t G, int32_t n_cg,
+                                int32_t n_ch, const float* cell, float* rmin, float* rmax, void* stream, int images);
+int aggf_gb_regmat_cols_cell(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                             int32_t G, int32_t n_cg, int32_t site, const float* sizes, int32_t n_id,
+                             const int32_t* cols, int32_t n_cols, const void* centers, int32_t n_basis,
+                             double width, double clip, double kbt, int32_t ld_feat, const void* cell, void* R3,
+                             int out_dtype, void* stream, int images);
+int aggf_gb_apply_cell(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                       int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, int32_t n_ch,
+                       const void* centers, int32_t n_basis, double width, double clip,
+                       const double* coef, int32_t n_feat, const void* cell, double* out, void* stream, int images);
+int aggf_gb_apply_cols_cell(const void* Fg, int f_dtype, const void* Pg, const void* cg, int g_dtype, int64_t T,
+                            int32_t G, int32_t n_cg, const float* sizes, int32_t n_id, const double* coef_id,
+                            const int32_t* col_ptr, const int32_t* col_idx, const double* col_val,
+                            const void* centers, int32_t n_basis, double width, double clip, const void* cell,
+                            double* out, void* stream, int images);
+
 /* ---------------------------------------------------------------------------
  * K3c  trjdot with a per-frame (3-D) factor.
  *
